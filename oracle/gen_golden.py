@@ -181,6 +181,105 @@ def run_model(ns, cfg, pano, shape, tag, train=True, subsample_out=None):
     return res
 
 
+# tests/test_oracle_vs_reference.py: the oracle against the reference on these models (fill tag "live").  Every output, the input
+# gradient and every parameter gradient is stored as a strided sample of at most LIVE_SAMPLE[kind] elements (all of them when it has
+# no more) with its stride, and the norm and max |.| of the whole tensor; each case with its configuration, so that the test reads
+# everything it needs from the fixture
+LIVE_CASES = [(TINY, True, (2, 3, 64, 128)), (TINY, False, (1, 3, 60, 100)), (TINY_PITCH, True, (2, 3, 64, 128)), (TINY, True, (1, 3, 100, 196))]
+LIVE_SAMPLE = {"out": 2048, "dx": 8192, "grad": 256}
+
+
+def live_case_key(cfg, pano, shape):
+    return f"{'pitch' if cfg is TINY_PITCH else 'tiny'}_{'pano' if pano else 'planar'}_{'x'.join(map(str, shape))}"
+
+
+def live_sample(t, n):
+    """(sample, step): at most n elements of t, every step-th one from the first (step 1 when t has no more than n; else odd, so
+    that the sample walks through every column of a tensor whose rows have a power-of-two length)."""
+    f = t.detach().reshape(-1)
+    step = 1 if f.numel() <= n else (f.numel() // n) | 1
+    return f[::step][:n].clone(), step
+
+
+def _live_store(out, key, kind, t):
+    out[key], out[f"{key}:step"] = live_sample(t, LIVE_SAMPLE[kind])
+    out[f"{key}:max"] = t.detach().abs().max().double()
+    out[f"{key}:norm"] = t.detach().double().norm()
+
+
+def live_ref_model(ns, cfg, pano):
+    m = ns.SimplePanoSwinTransformer(**cfg, pano_mode=pano)
+    for mod in m.modules():
+        if hasattr(mod, "sphere_position_alpha_table_Te"):
+            mod.sphere_position_alpha_table_Te = nn.Parameter(torch.zeros_like(mod.sphere_position_alpha_table_Te))
+            mod.sphere_position_beta_table_Te = nn.Parameter(torch.zeros_like(mod.sphere_position_beta_table_Te))
+    det_fill_module(m, "live")
+    nn.Module.train(m, True)
+    return m
+
+
+def gen_oracle_vs_reference(ns):
+    """oracle_vs_reference.npz (outputs / gradients, key "<case>:<what>") and reference_interface.json (the constructor's
+    parameters and defaults, the registry, state-dict keys / shapes / dtypes of the product's configurations)."""
+    import json
+    import panoswin_oracle as po
+    out = {}
+    for cfg, pano, shape in LIVE_CASES:
+        c = live_case_key(cfg, pano, shape)
+        out[f"{c}:config"] = np.array(json.dumps(dict(cfg=cfg, pano=pano, shape=list(shape)), sort_keys=True))
+        ref = live_ref_model(ns, cfg, pano)
+        # the test fills the oracle with det_fill_module(.., "live") instead of loading this state dict: same tensors
+        ora = po.SimplePanoSwinTransformerOracle(**cfg, pano_mode=pano)
+        det_fill_module(ora, "live")
+        rs, os_ = ref.state_dict(), ora.state_dict()
+        assert list(rs) == list(os_) and all(torch.equal(rs[k], os_[k]) for k in rs), c
+        x = det_uniform(shape, "live:x", 1.0).requires_grad_(True)
+        outs = ref(x)
+        ws = [det_uniform(tuple(o.shape), f"live:w{i}") for i, o in enumerate(outs)]
+        sum((a * w).sum() for a, w in zip(outs, ws)).backward()
+        for i, o in enumerate(outs):
+            _live_store(out, f"{c}:out{i}", "out", o)
+        _live_store(out, f"{c}:dx", "dx", x.grad)
+        # parameter gradients packed in named_parameters() order: the samples end to end, their lengths and strides, the max |.| and norm of
+        # every whole gradient (a parameter without a gradient: length 0, none = 1)
+        names, samples, steps, lens, gmax, gnorm, none = [], [], [], [], [], [], []
+        for k, p in ref.named_parameters():
+            names.append(k)
+            none.append(p.grad is None)
+            g = torch.zeros(0) if p.grad is None else p.grad
+            sample, step = live_sample(g, LIVE_SAMPLE["grad"])
+            samples.append(sample)
+            steps.append(step)
+            lens.append(samples[-1].numel())
+            gmax.append(float(g.abs().max()) if g.numel() else 0.0)
+            gnorm.append(float(g.double().norm()))
+        out[f"{c}:grad_names"] = np.array(names)
+        out[f"{c}:grad"] = torch.cat(samples)
+        out[f"{c}:grad_len"] = np.array(lens, np.int32)
+        out[f"{c}:grad_step"] = np.array(steps, np.int32)
+        out[f"{c}:grad_max"] = np.array(gmax, np.float64)
+        out[f"{c}:grad_norm"] = np.array(gnorm, np.float64)
+        out[f"{c}:grad_none"] = np.array(none, np.int8)
+    save("oracle_vs_reference", **out)
+
+    import inspect
+    sig = inspect.signature(ns.SimplePanoSwinTransformer.__init__).parameters
+    iface = {"registry": sorted(ns.BACKBONES.module_dict),
+             "init_parameters": list(sig),
+             "init_defaults": {k: repr(p.default) for k, p in sig.items() if k not in ("self", "norm_layer")},
+             "state_dicts": {}}
+    for name, cfg in (("tiny", TINY), ("tiny_pitch", TINY_PITCH), ("tiny_planar_noape", dict(TINY, ape=False, pano_mode=False)),
+                      ("tiny_out13", dict(TINY, out_indices=(1, 3))),
+                      ("T", dict(embed_dim=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24], ape=True))):
+        sd = ns.SimplePanoSwinTransformer(**cfg).state_dict()
+        iface["state_dicts"][name] = [[k, list(v.shape), str(v.dtype)] for k, v in sd.items()]
+    path = os.path.join(OUT, "reference_interface.json")
+    with open(path, "w") as f:
+        json.dump(iface, f, indent=0)
+        f.write("\n")
+    print(f"reference_interface.json  {os.path.getsize(path) / 1024:.1f} KiB")
+
+
 def main():
     """python oracle/gen_golden.py [name ...]: regenerate the named fixtures (default: all of them)."""
     ns = ref_loader.load_reference()
@@ -190,6 +289,7 @@ def main():
     torch.set_num_threads(8)
     jobs = {
         "index_maps": lambda: gen_index_maps(ns.hot),
+        "oracle_vs_reference": lambda: gen_oracle_vs_reference(ns),
         "geometry": lambda: gen_geometry(ns),
         "window_attention": lambda: gen_window_attention(ns.hot),
         "tiny_pano": lambda: save("tiny_pano", **run_model(ns, TINY, True, (2, 3, 64, 128), "tiny")),

@@ -4,10 +4,9 @@ TEST INFRASTRUCTURE ONLY.  Only ``tests/``, ``__graft_entry__.smoke()`` and the 
 ``bench.py`` may import this module -- as the checker, never as the thing measured or shipped.  The
 product package ``panoswintransformerobjectdetection_amd`` never imports it and has no CPU fallback.
 
-Pinning: this restatement is checked (tests/test_oracle_vs_reference.py, runs where
-``/root/reference`` exists) against the live reference imported through ``oracle/ref_loader.py``, and
-(everywhere, including the GPU box) against the fixtures in ``tests/golden/`` that
-``oracle/gen_golden.py`` captured from that live reference.  The reference's own known answers are
+Pinning: this restatement is checked (tests/test_oracle_vs_reference.py, tests/test_oracle_golden.py)
+against the fixtures in ``tests/golden/`` that ``oracle/gen_golden.py`` captured from the live reference
+imported through ``oracle/ref_loader.py``.  The reference's own known answers are
 re-checked too (HOT:105-115 relative-position index, HOT:162-171 uv grid, the WindowTransition
 round-trip of HOT:1276-1283, great_circle.py:108-118 city distances).
 
