@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSWIN_ABI_VERSION 2
+#define PSWIN_ABI_VERSION 3
 
 #define PSWIN_F32 0
 #define PSWIN_BF16 1
@@ -395,6 +395,74 @@ int pswin_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16,
 int pswin_adamw_flat_groups(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, const unsigned char* group_of,
                             int n_groups, const float* lr_mult, const float* decay_mult, double lr, double beta1, double beta2, double eps,
                             double weight_decay, const float* step, void* stream);
+
+/* ---- the training recipe on the device: lr schedule, gradient-norm clipping, non-finite guard -----------------------------------
+ * mmcv's LrUpdaterHook (configs/_base_/schedules/schedule_1x.py:5-10: policy 'step', linear warmup) and OptimizerHook(grad_clip)
+ * (mmdet/utils/optimizer.py:30-32 -> clip_grad_norm_) evaluated on the device, so that a captured step (hipGraph replay) follows
+ * them without a host synchronisation.  One step is up to three launches on `stream`:
+ *   pswin_grad_sumsq      (only with clipping or the guard)  gradient -> PSWIN_GRADSQ_PARTIALS f64 partial sums of squares
+ *   pswin_adamw_record    (one workgroup)                    partials + schedule + counters -> pswin_step_record
+ *   pswin_adamw_flat_sched                                   the AdamW update of pswin_adamw_flat_groups with the record's
+ *                                                            lr per group, step number t and clip coefficient
+ * Schedule, with i = the 0-based iteration about to run (`*iteration` before the record's increment), e = i / iters_per_epoch
+ * when by_epoch, base_k = lr * lr_mult[k]:
+ *   policy STEP:  progress = by_epoch ? e : i; exp = #{milestones s : progress >= s} (or progress / step_every when
+ *                 n_milestones = 0); regular_k = base_k * gamma^exp, then max(regular_k, min_lr) when has_min_lr
+ *   policy FIXED: regular_k = base_k
+ *   warmup, while i < warmup_iters: CONSTANT regular_k * ratio; LINEAR regular_k * (1 - (1 - i / warmup_iters) * (1 - ratio));
+ *                 EXP regular_k * ratio^(1 - i / warmup_iters)
+ * All of it in double.  The struct is a HOST pointer, copied into the kernel arguments. */
+#define PSWIN_LR_FIXED 0
+#define PSWIN_LR_STEP 1
+#define PSWIN_WARMUP_NONE 0
+#define PSWIN_WARMUP_CONSTANT 1
+#define PSWIN_WARMUP_LINEAR 2
+#define PSWIN_WARMUP_EXP 3
+#define PSWIN_LR_MAX_MILESTONES 8
+#define PSWIN_GRADSQ_PARTIALS 1024
+typedef struct pswin_lr_schedule {
+    int policy;                                 /* PSWIN_LR_FIXED / PSWIN_LR_STEP */
+    int warmup;                                 /* PSWIN_WARMUP_* */
+    int warmup_iters;                           /* in iterations (warmup_by_epoch already multiplied out); >= 1 with a warmup */
+    int by_epoch;                               /* the step policy counts epochs of iters_per_epoch iterations */
+    int iters_per_epoch;                        /* >= 1 when by_epoch */
+    int n_milestones;                           /* 0 .. PSWIN_LR_MAX_MILESTONES, ascending */
+    int step_every;                             /* n_milestones == 0: exp = progress / step_every (mmcv's int `step`); 0 = never */
+    int has_min_lr;
+    int milestones[PSWIN_LR_MAX_MILESTONES];
+    double warmup_ratio;
+    double gamma;
+    double min_lr;
+} pswin_lr_schedule;
+/* What one step applies, written by pswin_adamw_record into DEVICE memory (96 bytes, 8-byte aligned). */
+typedef struct pswin_step_record {
+    double lr[PSWIN_ADAMW_MAX_GROUPS];          /* scheduled lr of every parameter group (lr_mult included) */
+    double norm;                                /* 2-norm of the whole gradient before clipping; 0 when it was not computed */
+    float lr_base;                              /* (float)lr[0]: group 0 is the base group (lr_mult 1) */
+    float norm_f;                               /* (float)norm */
+    float coef;                                 /* clip coefficient min(1, max_norm / (norm + 1e-6)); 1 without clipping */
+    float t;                                    /* Adam step number the update uses (*step after the record) */
+    int applied;                                /* 0: the guard saw a non-finite norm and the update leaves everything alone */
+    int iteration;                              /* i of this step */
+} pswin_step_record;
+/* partials: DEVICE f64 [PSWIN_GRADSQ_PARTIALS]; partial b = sum of g[j]^2 over a fixed contiguous range of j, in a fixed order
+ * (bit-identical from run to run).  g: f32 [n], n a multiple of 4, 16-byte aligned. */
+int pswin_grad_sumsq(const float* g, long long n, double* partials, void* stream);
+/* One workgroup.  partials: the output of pswin_grad_sumsq, or NULL (then norm = 0, coef = 1, every step applied; max_norm must be
+ * <= 0 and skip_nonfinite 0).  max_norm > 0: clip; <= 0: no clipping.  Counters (DEVICE f32 scalars, exact up to 2^24):
+ * *iteration += 1 always; *step += 1 when the step is applied (always without skip_nonfinite, finite norm with it);
+ * *skipped += 1 otherwise.  lr: the base lr; lr_mult: HOST array of n_groups (1 .. PSWIN_ADAMW_MAX_GROUPS) multipliers, NULL = one
+ * group.  record: DEVICE. */
+int pswin_adamw_record(const double* partials, const pswin_lr_schedule* sched, double lr, int n_groups, const float* lr_mult,
+                       double max_norm, int skip_nonfinite, float* step, float* iteration, float* skipped, pswin_step_record* record,
+                       void* stream);
+/* The update of pswin_adamw_flat_groups (same arithmetic, same bf16 shadow write) with lr per group, t and the clip coefficient read
+ * from `record` (DEVICE): the gradient enters as g * coef in f32 and is not written back (the buffer keeps the unclipped gradient);
+ * record->applied == 0 leaves p, m, v and p_bf16 untouched.  decay_mult: HOST array of n_groups multipliers (NULL with group_of
+ * NULL, n_groups 0 = one group). */
+int pswin_adamw_flat_sched(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, const unsigned char* group_of,
+                           int n_groups, const float* decay_mult, double beta1, double beta2, double eps, double weight_decay,
+                           const pswin_step_record* record, void* stream);
 /* ---- the caller's side of the path: RoIAlign over an FPN pyramid ------------------------------------------------
  * configs/_base_/models/mask_rcnn_swin_fpn.py:44-48, 63-67 (SingleRoIExtractor, RoIAlign output 7 / 14, sampling_ratio = 0, strides
  * 4..32) and mmdet/models/roi_heads/roi_extractors/single_level_roi_extractor.py:78-108.  RoIAlign itself is mmcv.ops (not in the

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PSWIN_LIB") or os.path.join(_PKG, "libpswin_hip.so") 
 F32, BF16 = 0, 1
 MODE_PLANAR, MODE_PANO = 0, 1
 WS, WTOK, WPAD, HEAD_DIM = 7, 49, 64, 32
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -71,6 +71,10 @@ _PROTOTYPES = {
     "pswin_adamw_flat": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp],
     "pswin_adamw_flat_groups": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _i, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp],
+    "pswin_grad_sumsq": [_vp, ctypes.c_longlong, _vp, _vp],
+    "pswin_adamw_record": [_vp, _vp, ctypes.c_double, _i, _vp, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp],
+    "pswin_adamw_flat_sched": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _i, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                               ctypes.c_double, _vp, _vp],
     "pswin_roi_align_supported": [_i, _i],
     "pswin_roi_align_fwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
     "pswin_roi_align_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
@@ -146,6 +150,19 @@ class TnJob(ctypes.Structure):
 class TransposeJob(ctypes.Structure):
     """pswin_transpose_job of include/pswin.h"""
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("rows", ctypes.c_int), ("cols", ctypes.c_int)]
+
+
+class LrSchedule(ctypes.Structure):
+    """pswin_lr_schedule of include/pswin.h"""
+    _fields_ = [("policy", ctypes.c_int), ("warmup", ctypes.c_int), ("warmup_iters", ctypes.c_int), ("by_epoch", ctypes.c_int),
+                ("iters_per_epoch", ctypes.c_int), ("n_milestones", ctypes.c_int), ("step_every", ctypes.c_int), ("has_min_lr", ctypes.c_int),
+                ("milestones", ctypes.c_int * 8), ("warmup_ratio", ctypes.c_double), ("gamma", ctypes.c_double), ("min_lr", ctypes.c_double)]
+
+
+class StepRecord(ctypes.Structure):
+    """pswin_step_record of include/pswin.h (lives in device memory; the layout locates its fields)"""
+    _fields_ = [("lr", ctypes.c_double * 8), ("norm", ctypes.c_double), ("lr_base", ctypes.c_float), ("norm_f", ctypes.c_float),
+                ("coef", ctypes.c_float), ("t", ctypes.c_float), ("applied", ctypes.c_int), ("iteration", ctypes.c_int)]
 
 
 class RoiLevels(ctypes.Structure):
