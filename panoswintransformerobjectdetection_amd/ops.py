@@ -837,20 +837,25 @@ def gemm_nt_supported(x2d, n_out):
             and bool(_lib.load().pswin_gemm_nt_supported(x2d.shape[0], x2d.shape[1], n_out)))
 
 
-def gemm_nt_tile(M, K, N):
-    """Row-tile height (64 / 128) with which pswin_gemm_nt computes [M, K] x [N, K]^T, or 0 = leave it to the library.
+# the row tiles each entry point of the tiled GEMM accepts (csrc/pswin_gemm_nt.hip): 96-row tiles exist for the plain epilogue only
+GEMM_NT_TILES = {"pswin_gemm_nt": (64, 96, 128), "pswin_gemm_nt_f32": (64, 128),
+                 "pswin_gemm_nt_gelu_fwd": (64, 128), "pswin_gemm_nt_gelu_bwd": (64, 128)}
+
+
+def gemm_nt_tile(M, K, N, entry="pswin_gemm_nt", required=False):
+    """Row-tile height (one of GEMM_NT_TILES[entry]) with which `entry` computes [M, K] x [N, K]^T, or 0 = leave it to the library.
+    required=True: the product has no library counterpart (the fused GELU forms): gemm_nt_rows where the rule would answer 0.
     From profiles/r02_gemm_nt_vs_library.txt (MI355X, PanoSwin-T shapes at batch 8) and the in-step A/Bs of round 4
     (profiles/r04_ab_runs.json: gemm_nt_*): the HIP kernel wins wherever the rows fill the chip (M >= 8192: stages 1-2), on the narrow
     outputs with a short contraction at 4-6 k rows, and wherever 128-row tiles still give every CU two rounds of work (stage 3's qkv / fc1
     at batch 8); 128-row tiles then, or when they make the launch fit the chip ONCE (<= 256 tiles: the kernel's four-stage form,
-    csrc/pswin_gemm_nt.hip) while 64-row tiles would not; 64-row tiles otherwise."""
-    if not GEMM_NT or not bool(_lib.load().pswin_gemm_nt_supported(M, K, N)):
-        return 0
-    t128 = -(-M // 128) * (N // 192)
-    if M < 8192 and not (N <= 768 and K <= 1536) and t128 < 512:
-        return 0
-    rows = gemm_nt_rows(M, N)
-    if rows == 64:
+    csrc/pswin_gemm_nt.hip) while 64-row tiles would not; 96-row tiles where the entry has them and 64-row tiles would spill into a
+    second round; 64-row tiles otherwise."""
+    rows, t128 = gemm_nt_rows(M, N), -(-M // 128) * (N // 192)
+    if (not GEMM_NT or not bool(_lib.load().pswin_gemm_nt_supported(M, K, N))
+            or (M < 8192 and not (N <= 768 and K <= 1536) and t128 < 512)):
+        return rows if required else 0
+    if rows == 64 and 96 in GEMM_NT_TILES[entry]:
         # 64-row tiles that spill into a second, mostly empty round of the 512 tile slots (two workgroups per CU): 96-row tiles in one
         t64, t96 = -(-M // 64) * (N // 192), -(-M // 96) * (N // 192)
         if 512 < t64 <= 768 and t96 <= 512:
@@ -859,7 +864,7 @@ def gemm_nt_tile(M, K, N):
 
 
 def gemm_nt_rows(M, N):
-    """the row-tile height for a product that runs on pswin_gemm_nt in any case (the fused GELU forms have no library counterpart)"""
+    """the row-tile height of the tiled GEMM's 64 / 128-row forms for a product that runs on it in any case"""
     t64, t128 = -(-M // 64) * (N // 192), -(-M // 128) * (N // 192)
     if t128 < 512 and t64 > 256 and t128 <= 256:
         return 128
@@ -1019,6 +1024,24 @@ def skinny_gemm(x2d, w, bias=None, transpose_w=False):
     return y
 
 
+def linear_product(x2d, wb, bias=None, b_lp=None, out_f32=False, skinny=False):
+    """y = x2d @ wb^T (+ bias) on the first kernel that takes the shape: the streaming GEMM (skinny=True; the stage-0 shapes), the
+    tiled HIP GEMM where gemm_nt_tile picks it (stages 1-3), else the library GEMM (with b_lp, bias's bf16 copy, if given).
+    out_f32: an f32 result where the tiled HIP GEMM runs (its epilogue writes it), a cast of the bf16 result elsewhere."""
+    M, K = x2d.shape
+    N = wb.shape[0]
+    if skinny and skinny_gemm_supported(x2d, N):
+        y = skinny_gemm(x2d, wb, bias)
+        return y.float() if out_f32 else y
+    tile = gemm_nt_tile(M, K, N, "pswin_gemm_nt_f32" if out_f32 else "pswin_gemm_nt") if x2d.dtype == torch.bfloat16 else 0
+    if tile:
+        return gemm_nt(x2d, wb, bias, tile, out_f32=out_f32)
+    bb = None if bias is None else (b_lp if b_lp is not None else bias.to(x2d.dtype))
+    with _lib.timed("lib_gemm_fwd", 2 * (M * K + M * N + N * K), 2 * M * K * N):
+        y = F.linear(x2d, wb, bb)
+    return y.float() if out_f32 else y
+
+
 def _pick_split(M, n_tiles):
     """Number of K-splits for a weight-gradient GEMM with contraction length M and n_tiles output tiles: a divisor
     of M that gives hipBLASLt about a thousand independent tiles while each split keeps >= 512 rows."""
@@ -1040,7 +1063,6 @@ class _LinearSplitK(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, w_lp, b_lp, zero_bias_cols=None, w_lp_t=None, out_f32=False):
-        # out_f32: an f32 result where the tiled HIP GEMM runs (its epilogue writes it), a cast of the bf16 result elsewhere
         # w_lp / b_lp: this step's bf16 copies of the fp32 master parameters (refreshed by ONE multi-tensor cast per
         # forward, see SimplePanoSwinTransformer._refresh_lowp); gradients go to the fp32 masters.
         wb = w_lp if w_lp is not None else weight.to(x.dtype)
@@ -1048,17 +1070,7 @@ class _LinearSplitK(torch.autograd.Function):
         ctx.has_bias = bias is not None
         ctx.zero_bias_cols = zero_bias_cols
         ctx.weight, ctx.bias = weight, bias                 # for grad_slot / owners: dW may be summed straight into its flat slot
-        if skinny_gemm_supported(x, wb.shape[0]):       # stage-0 shapes: streaming HIP GEMM, weight resident in LDS
-            y = skinny_gemm(x, wb, bias)
-            return y.float() if out_f32 else y
-        tile = gemm_nt_tile(x.shape[0], x.shape[1], wb.shape[0]) if x.dtype == torch.bfloat16 else 0
-        if tile:                                        # stages 1-3: tiled HIP GEMM where it beats the library kernel
-            return gemm_nt(x, wb, bias, tile, out_f32=out_f32)
-        bb = None if bias is None else (b_lp if b_lp is not None else bias.to(x.dtype))
-        M, K, N = x.shape[0], x.shape[1], wb.shape[0]
-        with _lib.timed("lib_gemm_fwd", 2 * (M * K + M * N + N * K), 2 * M * K * N):
-            y = F.linear(x, wb, bb)
-        return y.float() if out_f32 else y
+        return linear_product(x, wb, bias, b_lp, out_f32, skinny=True)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1090,8 +1102,15 @@ def linear_backward(x, wb, dy, weight, bias, zero_bias_cols, need_dx, wbt=None):
             with _lib.timed("lib_gemm_dgrad", 2 * (M * K + M * N + N * K), 2 * M * K * N):
                 dx = dy @ wb
     queued = queue_weight_gradient(dy, x, weight, bias, zero_bias_cols)
-    if queued is not None:
-        return dx, queued[0], queued[1]
+    return (dx, *(queued if queued is not None else weight_gradient(dy, x, weight, bias, zero_bias_cols)))
+
+
+def weight_gradient(dy, x, weight, bias=None, zero_bias_cols=None):
+    """dW = dy^T x (f32 [N, K]) and the bias gradient (f32 [N] or None), launched now: the ring kernel (the bias gradient rides along),
+    else the library's batched GEMM over row chunks or a plain GEMM; a split's partial slabs summed by sum_rows.  weight / bias: the
+    fp32 master parameters the gradients belong to (grad_slot / deferred reductions)."""
+    M, N = dy.shape
+    K = x.shape[1]
     sp = 0
     rs = gemm_tn_ring_splits(M, N, K) if dy.dtype == torch.bfloat16 else 0
     db_part = None
@@ -1119,7 +1138,7 @@ def linear_backward(x, wb, dy, weight, bias, zero_bias_cols, need_dx, wbt=None):
         db = sum_rows(db_part, db_part.shape[0], N, owners=(bias,))
     else:
         db = colsum(dy, zero_bias_cols, owners=(bias,)) if bias is not None else None
-    return dx, dw, db
+    return dw, db
 
 
 def linear(x, lin, cd, use_bias=True, zero_bias_cols=None, out_f32=False):
@@ -1129,12 +1148,16 @@ def linear(x, lin, cd, use_bias=True, zero_bias_cols=None, out_f32=False):
     if cd == torch.float32:
         return F.linear(x.float(), lin.weight, lin.bias if use_bias else None)
     shp = x.shape
-    x2 = x.to(cd).reshape(-1, shp[-1])
-    lp = lin.__dict__.get("_lowp")
-    w_lp, b_lp = lp if lp is not None else (None, None)
-    bias = lin.bias if use_bias else None
-    return _LinearSplitK.apply(x2, lin.weight, bias, w_lp, b_lp if use_bias else None, zero_bias_cols,
-                               lin.__dict__.get("_lowp_t"), out_f32).view(*shp[:-1], lin.weight.shape[0])
+    w_lp, b_lp, w_lp_t = _lowp(lin)
+    return _LinearSplitK.apply(x.to(cd).reshape(-1, shp[-1]), lin.weight, lin.bias if use_bias else None, w_lp,
+                               b_lp if use_bias else None, zero_bias_cols, w_lp_t, out_f32).view(*shp[:-1], lin.weight.shape[0])
+
+
+def _lowp(lin):
+    """(weight, bias, transposed weight): this step's bf16 shadows of an nn.Linear's fp32 parameters (SimplePanoSwinTransformer.
+    _refresh_lowp / _refresh_transposed), None where the Linear has none"""
+    w_lp, b_lp = lin.__dict__.get("_lowp") or (None, None)
+    return w_lp, b_lp, lin.__dict__.get("_lowp_t")
 
 
 class _Fc1Gelu(torch.autograd.Function):
@@ -1168,22 +1191,7 @@ class _Fc1Gelu(torch.autograd.Function):
              algo_bytes=2 * M * (K + 2 * N))
         db = sum_rows(ws, lib.pswin_fc1_gelu_partial_rows(M), N, owners=(ctx.bias,))
         dx = skinny_gemm(dy, wb, None, transpose_w=True) if ctx.needs_input_grad[0] else None
-        rs = gemm_tn_ring_splits(M, N, K)
-        if rs:                                                   # the ring kernel's stage-0 geometry: the whole [N, K] gradient per workgroup
-            part, ch = gemm_tn_ring(dy, x, rs, torch.bfloat16 if (GEMM_TN_RING_BF16 and rs > 1) else torch.float32), rs
-            if ch == 1:
-                dw = part.view(N, K).float()
-        else:
-            ch = _pick_split(M, -(-N // 64) * -(-K // 64))
-            with _lib.timed("lib_gemm_wgrad", 2 * (M * K + M * N) + 4 * N * K, 2 * M * K * N):
-                if ch > 1:
-                    part = torch.bmm(dy.view(ch, M // ch, N).transpose(1, 2), x.view(ch, M // ch, K))
-                else:
-                    dw = (dy.t() @ x).float()
-        if ch > 1:
-            dw = sum_rows(part, ch, N * K, out=grad_slot(ctx.weight), owners=(ctx.weight,)).view(N, K)
-        else:
-            flush_if_pending((ctx.weight,))
+        dw, _ = weight_gradient(dy, x, ctx.weight)               # launched here, never queued for the grouped end-of-pass launch
         return dx, dw, db, None
 
 
@@ -1258,8 +1266,7 @@ def mlp0_fused_supported(x2d, hidden):
 
 def mlp0_fused(x2d, fc1, fc2):
     """fc2_nobias(gelu(fc1(x2d))) for the stage-0 Mlp as one autograd node: see _Mlp0."""
-    l1, l2 = fc1.__dict__.get("_lowp"), fc2.__dict__.get("_lowp")
-    return _Mlp0.apply(x2d, fc1.weight, fc1.bias, fc2.weight, l1[0] if l1 is not None else None, l2[0] if l2 is not None else None)
+    return _Mlp0.apply(x2d, fc1.weight, fc1.bias, fc2.weight, _lowp(fc1)[0], _lowp(fc2)[0])
 
 
 def fc1_gelu_shape_ok(M, K, N):
@@ -1289,16 +1296,39 @@ class _BiasGelu(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dh):
         y, b = ctx.saved_tensors
-        M, N = y.numel() // y.shape[-1], y.shape[-1]
-        dh = dh.to(y.dtype).contiguous()
-        dy = torch.empty_like(y)
-        lib = _lib.load()
-        ws = torch.empty(lib.pswin_bias_gelu_workspace(M, N), dtype=torch.float32, device=y.device)
-        call("pswin_bias_gelu_bwd", y, ptr(dh), ptr(y), dtype_code(y), ptr(b), ptr(dy), None, ptr(ws), M, N,
-             algo_bytes=3 * y.numel() * y.element_size())
-        db = sum_rows(ws, lib.pswin_bias_gelu_partial_rows(M, N, dtype_code(y)), N, owners=(ctx.bias,)) \
-            if b is not None else None
-        return dy, db
+        return bias_gelu_backward(y, dh.to(y.dtype).contiguous(), b, ctx.bias)
+
+
+def bias_gelu_backward(y, dh, b, bias):
+    """(dL/dy, the bias gradient f32 [N] or None without b) of h = gelu(y + b) for y, dh [..., N] (pswin_bias_gelu_bwd); b: the f32 bias
+    the forward pass added, bias the parameter it came from"""
+    M, N = y.numel() // y.shape[-1], y.shape[-1]
+    dy = torch.empty_like(y)
+    lib = _lib.load()
+    ws = torch.empty(lib.pswin_bias_gelu_workspace(M, N), dtype=torch.float32, device=y.device)
+    call("pswin_bias_gelu_bwd", y, ptr(dh), ptr(y), dtype_code(y), ptr(b), ptr(dy), None, ptr(ws), M, N,
+         algo_bytes=3 * y.numel() * y.element_size())
+    return dy, (sum_rows(ws, lib.pswin_bias_gelu_partial_rows(M, N, dtype_code(y)), N, owners=(bias,)) if b is not None else None)
+
+
+def gelu_data_gradient(dout, wb, wbt, pre, b, b1):
+    """Backward of out = gelu(pre + b) @ wb^T (fc2 without its bias over fc1's bias + GELU) as far as pre: (dL/dpre, fc1's bias gradient
+    f32 [N] or None without b).  dout [M, C], wb [C, N], pre [M, N] bf16; b: the f32 bias the forward pass added, b1 its parameter.
+    wbt = wb^T: fc2's data gradient, the GELU backward and the bias-gradient partial rows in ONE kernel (pswin_gemm_nt_gelu_bwd);
+    None: the library GEMM, then pswin_bias_gelu_bwd."""
+    M, N = pre.shape
+    C = wb.shape[0]
+    if wbt is None:
+        with _lib.timed("lib_gemm_dgrad", 2 * (M * N + M * C + N * C), 2 * M * N * C):
+            dh = dout @ wb
+        return bias_gelu_backward(pre, dh, b, b1)
+    tile = gemm_nt_tile(M, C, N, "pswin_gemm_nt_gelu_bwd", required=True)
+    dpre = torch.empty_like(pre)
+    rows = _lib.load().pswin_gemm_nt_partial_rows(M, tile)
+    ws = torch.empty(rows, N, dtype=torch.float32, device=pre.device)
+    call("pswin_gemm_nt_gelu_bwd", pre, ptr(dout), ptr(wbt), ptr(pre), ptr(b), ptr(dpre), ptr(ws), M, C, N, tile,
+         algo_bytes=2 * (M * C + 2 * M * N + N * C), algo_flops=2 * M * N * C)
+    return dpre, (sum_rows(ws, rows, N, owners=(b1,)) if b is not None else None)
 
 
 class _BiasGeluLinear(torch.autograd.Function):
@@ -1317,16 +1347,10 @@ class _BiasGeluLinear(torch.autograd.Function):
         b = None if b1 is None else b1.detach().float().contiguous()
         call("pswin_bias_gelu_fwd", y2, ptr(y2), dtype_code(y2), ptr(b), ptr(h), M, N, algo_bytes=2 * y2.numel() * y2.element_size())
         wb = w2_lp if w2_lp is not None else w2.to(y.dtype)
-        C = wb.shape[0]
-        tile = gemm_nt_tile(M, N, C)
-        if tile:
-            out = gemm_nt(h, wb, None, tile)
-        else:
-            with _lib.timed("lib_gemm_fwd", 2 * (M * N + M * C + N * C), 2 * M * N * C):
-                out = F.linear(h, wb)
+        out = linear_product(h, wb)
         ctx.save_for_backward(y2, b, h, wb, w2_lp_t)
         ctx.params = (b1, w2)
-        return out.view(*shp[:-1], C)
+        return out.view(*shp[:-1], wb.shape[0])
 
     @staticmethod
     def backward(ctx, dout):
@@ -1335,25 +1359,9 @@ class _BiasGeluLinear(torch.autograd.Function):
         M, N = y2.shape
         C = wb.shape[0]
         dout = dout.reshape(M, C).contiguous()
-        lib = _lib.load()
-        tile = 0
-        if wbt is not None and GEMM_NT and lib.pswin_gemm_nt_supported(M, C, N):
-            tile = gemm_nt_tile(M, C, N) or gemm_nt_rows(M, N)        # (the narrow stage-3 case the plain rule leaves to the library: fused it wins)
-        if tile:
-            dpre = torch.empty_like(y2)
-            rows = lib.pswin_gemm_nt_partial_rows(M, tile)
-            ws = torch.empty(rows, N, dtype=torch.float32, device=y2.device)
-            call("pswin_gemm_nt_gelu_bwd", y2, ptr(dout), ptr(wbt), ptr(y2), ptr(b), ptr(dpre), ptr(ws), M, C, N, tile,
-                 algo_bytes=2 * (M * C + 2 * M * N + N * C), algo_flops=2 * M * N * C)
-            db = sum_rows(ws, rows, N, owners=(b1,)) if b is not None else None
-        else:
-            with _lib.timed("lib_gemm_dgrad", 2 * (M * N + M * C + N * C), 2 * M * N * C):
-                dh = dout @ wb
-            dpre = torch.empty_like(y2)
-            ws = torch.empty(lib.pswin_bias_gelu_workspace(M, N), dtype=torch.float32, device=y2.device)
-            call("pswin_bias_gelu_bwd", y2, ptr(dh), ptr(y2), dtype_code(y2), ptr(b), ptr(dpre), None, ptr(ws), M, N,
-                 algo_bytes=3 * y2.numel() * y2.element_size())
-            db = sum_rows(ws, lib.pswin_bias_gelu_partial_rows(M, N, dtype_code(y2)), N, owners=(b1,)) if b is not None else None
+        # fused even in the narrow stage-3 case the plain rule leaves to the library
+        fused = wbt is not None and GEMM_NT and bool(_lib.load().pswin_gemm_nt_supported(M, C, N))
+        dpre, db = gelu_data_gradient(dout, wb, wbt if fused else None, y2, b, b1)
         _, dw, _ = linear_backward(h, wb, dout, w2, None, None, False)
         return dpre.view_as(y2), db, dw, None, None
 
@@ -1370,18 +1378,14 @@ class _MlpFused(torch.autograd.Function):
         M, K = x.shape
         w1b = w1_lp if w1_lp is not None else w1.to(x.dtype)
         w2b = w2_lp if w2_lp is not None else w2.to(x.dtype)
-        N, C = w1b.shape[0], w2b.shape[0]
+        N = w1b.shape[0]
         b = b1.detach().float().contiguous()
         pre = torch.empty(M, N, dtype=x.dtype, device=x.device)
         h = torch.empty_like(pre)
-        call("pswin_gemm_nt_gelu_fwd", x, ptr(x), ptr(w1b), ptr(b), ptr(pre), ptr(h), M, K, N, gemm_nt_tile(M, K, N) or gemm_nt_rows(M, N),
+        tile = gemm_nt_tile(M, K, N, "pswin_gemm_nt_gelu_fwd", required=True)
+        call("pswin_gemm_nt_gelu_fwd", x, ptr(x), ptr(w1b), ptr(b), ptr(pre), ptr(h), M, K, N, tile,
              algo_bytes=2 * (M * K + 2 * M * N + N * K), algo_flops=2 * M * K * N)
-        tile = gemm_nt_tile(M, N, C)
-        if tile:
-            out = gemm_nt(h, w2b, None, tile)
-        else:
-            with _lib.timed("lib_gemm_fwd", 2 * (M * N + M * C + N * C), 2 * M * N * C):
-                out = F.linear(h, w2b)
+        out = linear_product(h, w2b)
         ctx.save_for_backward(x, pre, h, b, w1b, w1_lp_t, w2b, w2_lp_t)
         ctx.params = (w1, b1, w2)
         return out
@@ -1390,26 +1394,8 @@ class _MlpFused(torch.autograd.Function):
     def backward(ctx, dout):
         x, pre, h, b, w1b, w1bt, w2b, w2bt = ctx.saved_tensors
         w1, b1, w2 = ctx.params
-        M, N = pre.shape
-        C = w2b.shape[0]
         dout = dout.contiguous()
-        lib = _lib.load()
-        if w2bt is not None:
-            tile = gemm_nt_tile(M, C, N) or gemm_nt_rows(M, N)
-            dpre = torch.empty_like(pre)
-            rows = lib.pswin_gemm_nt_partial_rows(M, tile)
-            ws = torch.empty(rows, N, dtype=torch.float32, device=pre.device)
-            call("pswin_gemm_nt_gelu_bwd", pre, ptr(dout), ptr(w2bt), ptr(pre), ptr(b), ptr(dpre), ptr(ws), M, C, N, tile,
-                 algo_bytes=2 * (M * C + 2 * M * N + N * C), algo_flops=2 * M * N * C)
-            db = sum_rows(ws, rows, N, owners=(b1,))
-        else:
-            with _lib.timed("lib_gemm_dgrad", 2 * (M * N + M * C + N * C), 2 * M * N * C):
-                dh = dout @ w2b
-            dpre = torch.empty_like(pre)
-            ws = torch.empty(lib.pswin_bias_gelu_workspace(M, N), dtype=torch.float32, device=pre.device)
-            call("pswin_bias_gelu_bwd", pre, ptr(dh), ptr(pre), dtype_code(pre), ptr(b), ptr(dpre), None, ptr(ws), M, N,
-                 algo_bytes=3 * pre.numel() * pre.element_size())
-            db = sum_rows(ws, lib.pswin_bias_gelu_partial_rows(M, N, dtype_code(pre)), N, owners=(b1,))
+        dpre, db = gelu_data_gradient(dout, w2b, w2bt, pre, b, b1)     # fused: mlp_fused_supported checked the shape
         _, dw2, _ = linear_backward(h, w2b, dout, w2, None, None, False)
         dx, dw1, _ = linear_backward(x, w1b, dpre, w1, None, None, ctx.needs_input_grad[0], w1bt)
         return dx, dw1, db, dw2, None, None, None, None
@@ -1422,16 +1408,14 @@ def mlp_fused_supported(x2d, hidden):
 
 def mlp_fused(x2d, fc1, fc2):
     """fc2_nobias(gelu(fc1(x2d))) as one autograd node on the tiled GEMM kernels: see _MlpFused."""
-    l1, l2 = fc1.__dict__.get("_lowp"), fc2.__dict__.get("_lowp")
-    return _MlpFused.apply(x2d, fc1.weight, fc1.bias, fc2.weight, l1[0] if l1 is not None else None, fc1.__dict__.get("_lowp_t"),
-                           l2[0] if l2 is not None else None, fc2.__dict__.get("_lowp_t"))
+    (w1_lp, _, w1_lp_t), (w2_lp, _, w2_lp_t) = _lowp(fc1), _lowp(fc2)
+    return _MlpFused.apply(x2d, fc1.weight, fc1.bias, fc2.weight, w1_lp, w1_lp_t, w2_lp, w2_lp_t)
 
 
 def bias_gelu_linear(y, bias1, lin2):
     """lin2(gelu(y + bias1)) without lin2's bias (bf16 rows): see _BiasGeluLinear."""
-    lp = lin2.__dict__.get("_lowp")
-    out = _BiasGeluLinear.apply(y.reshape(-1, y.shape[-1]), bias1, lin2.weight, lp[0] if lp is not None else None,
-                                lin2.__dict__.get("_lowp_t"))
+    w_lp, _, w_lp_t = _lowp(lin2)
+    out = _BiasGeluLinear.apply(y.reshape(-1, y.shape[-1]), bias1, lin2.weight, w_lp, w_lp_t)
     return out.view(*y.shape[:-1], lin2.weight.shape[0])
 
 
@@ -1706,12 +1690,10 @@ def window_attention_fused_supported(x2d, heads):
 def window_attention_fused(x2d, attn, dist, mask, n_bias_windows):
     """proj(attention(qkv(x2d))) WITHOUT the proj bias for window rows x2d [n*49, C] and the parameter holder `attn`
     (qkv, proj, the two tables, num_heads, scale): see _WindowAttentionFused."""
-    lq, lp = attn.qkv.__dict__.get("_lowp"), attn.proj.__dict__.get("_lowp")
     return _WindowAttentionFused.apply(x2d, attn.qkv.weight, attn.qkv.bias, attn.proj.weight,
                                        attn.sphere_position_alpha_table_Te, attn.sphere_position_beta_table_Te,
                                        _as_tiles(dist), _as_tiles(mask), attn.num_heads, attn.scale, n_bias_windows,
-                                       lq[0] if lq is not None else None, lp[0] if lp is not None else None,
-                                       torch.is_grad_enabled())
+                                       _lowp(attn.qkv)[0], _lowp(attn.proj)[0], torch.is_grad_enabled())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1864,8 +1846,7 @@ def window_attention_qkv_fused_supported(x2d, heads):
 def window_attention_qkv_fused(x2d, attn, dist, mask, n_bias_windows):
     """attention(qkv(x2d)) -- everything of WindowAttention.forward in front of self.proj -- for window rows x2d [n*49, C] and the
     parameter holder `attn`: see _WindowAttentionQkvFused."""
-    lq = attn.qkv.__dict__.get("_lowp")
+    wq_lp, _, wq_lp_t = _lowp(attn.qkv)
     return _WindowAttentionQkvFused.apply(x2d, attn.qkv.weight, attn.qkv.bias, attn.sphere_position_alpha_table_Te,
                                           attn.sphere_position_beta_table_Te, _as_tiles(dist), _as_tiles(mask), attn.num_heads, attn.scale,
-                                          n_bias_windows, lq[0] if lq is not None else None, attn.qkv.__dict__.get("_lowp_t"),
-                                          torch.is_grad_enabled())
+                                          n_bias_windows, wq_lp, wq_lp_t, torch.is_grad_enabled())

@@ -962,6 +962,36 @@ def test_linear_on_the_tiled_gemm_matches_the_library_path(ops):
         assert torch.allclose(u, v, rtol=2e-2, atol=2e-2 * float(v.abs().max()))
 
 
+def test_linear_with_an_f32_result_where_the_rule_picks_96_row_tiles(ops):
+    """PatchMerging.reduction 0 -> 1 at batch 5, 512 x 1024 (M = 40960, 384 -> 192, out_f32): the plain tile rule gives 96-row tiles,
+    which pswin_gemm_nt_f32 does not have; ops.linear runs its 64-row form and matches the library path (output and gradients)."""
+    import torch.nn as nn
+    torch.manual_seed(5)
+    M, K, N = 40960, 384, 192
+    lin = nn.Linear(K, N, bias=False).to(DEV)
+    lin.__dict__["_lowp"] = (lin.weight.detach().to(torch.bfloat16), None)
+    wt = lin.__dict__["_lowp"][0].t().contiguous()
+    x = torch.randn(M, K, device=DEV).to(torch.bfloat16)
+    g = torch.randn(M, N, device=DEV)
+
+    def run(nt):
+        prev, ops.GEMM_NT = ops.GEMM_NT, nt
+        lin.__dict__["_lowp_t"] = wt if nt else None
+        try:
+            xx = x.clone().requires_grad_(True)
+            lin.weight.grad = None
+            y = ops.linear(xx, lin, torch.bfloat16, out_f32=True)
+            assert y.dtype == torch.float32
+            y.backward(g)
+            return y.detach(), xx.grad.float(), lin.weight.grad.clone()
+        finally:
+            ops.GEMM_NT = prev
+    assert ops.gemm_nt_tile(M, K, N) == 96 and ops.gemm_nt_tile(M, K, N, "pswin_gemm_nt_f32") == 64
+    a, b = run(True), run(False)
+    for u, v in zip(a, b):
+        assert torch.allclose(u, v, rtol=2e-2, atol=2e-2 * float(v.abs().max()))
+
+
 def test_gemm_tn_ring_jobs_one_launch_equals_the_single_launches(ops):
     """pswin_gemm_tn_ring_jobs (round 4): many independent weight gradients in one launch per tile geometry.  Eleven jobs of all three
     geometries, ragged M, 1 .. 40 splits, f32 and bf16 slabs, with and without bias sums / zero ranges, listed in an arbitrary order
@@ -1279,6 +1309,42 @@ def test_fc1_with_the_gelu_in_its_epilogue(ops, M, C, tile):
         assert torch.allclose(u, v, rtol=2e-2, atol=2e-2 * float(v.abs().max())), (u - v).abs().max()
     with torch.no_grad():
         assert torch.equal(ops.mlp_fused(x, fc1, fc2), a[0].to(torch.bfloat16))
+
+
+def test_mlp_where_the_rule_picks_96_row_tiles(ops):
+    """stage-1 Mlp at batch 2, 384 x 768 (M = 9216, C = 192): the plain tile rule gives fc1 96-row tiles, which the GELU forms of the
+    tiled GEMM do not have.  ops.mlp_fused and ops.bias_gelu_linear run their 64-row forms and match the unfused chain linear ->
+    bias_gelu -> linear (output and every gradient)."""
+    import torch.nn as nn
+    torch.manual_seed(9216)
+    M, C = 9216, 192
+    N = 4 * C
+    assert ops.gemm_nt_tile(M, C, N) == 96
+    fc1, fc2 = nn.Linear(C, N).to(DEV), nn.Linear(N, C).to(DEV)
+    for lin in (fc1, fc2):
+        wb = lin.weight.detach().to(torch.bfloat16)
+        lin.__dict__["_lowp"] = (wb, None)
+        lin.__dict__["_lowp_t"] = wb.t().contiguous()
+    x = torch.randn(M, C, device=DEV).to(torch.bfloat16)
+    g = torch.randn(M, C, device=DEV).to(torch.bfloat16)
+    assert ops.mlp_fused_supported(x, N)
+
+    def run(path):
+        xx = x.clone().requires_grad_(True)
+        for p in (*fc1.parameters(), *fc2.parameters()):
+            p.grad = None
+        if path == "mlp_fused":
+            out = ops.mlp_fused(xx, fc1, fc2)
+        elif path == "bias_gelu_linear":
+            out = ops.bias_gelu_linear(ops.linear(xx, fc1, torch.bfloat16, use_bias=False), fc1.bias, fc2)
+        else:
+            out = ops.linear(ops.bias_gelu(ops.linear(xx, fc1, torch.bfloat16, use_bias=False), fc1.bias), fc2, torch.bfloat16, use_bias=False)
+        out.backward(g)
+        return out.detach().float(), xx.grad.float(), fc1.weight.grad.clone(), fc1.bias.grad.clone(), fc2.weight.grad.clone()
+    ref = run("chain")
+    for path in ("mlp_fused", "bias_gelu_linear"):
+        for u, v in zip(run(path), ref):
+            assert torch.allclose(u, v, rtol=2e-2, atol=2e-2 * float(v.abs().max())), (path, (u - v).abs().max())
 
 
 def test_flat_adamw_matches_torch_adamw(ops):
