@@ -707,6 +707,28 @@ typedef struct pswin_table_grad_job {
 } pswin_table_grad_job;
 int pswin_attn_table_grads_batch(const pswin_table_grad_job* jobs, int n_jobs, int stages, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Panorama training augmentation (the image side of the PanoSwin data pipeline; the boxes stay on the host:
+ * panoswintransformerobjectdetection_amd/pano_aug.py)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* PanoStretch + RollAug + RandomFlip of mmdet/datasets/pipelines/transforms.py:992-1068 and the recipe's RandomFlip in one gather:
+ *   dst[b][y][x][:] = S_b[y][xs][:],  xs = ((flip ? W-1-x : x) - shift) mod W,
+ * S_b = the stretch of src[b] by (kx, ky) (lzx/yolo/extensions/xzaug.py getAug: float64 coordinates, order-1 map_coordinates with
+ * scipy's 'wrap' boundary of period n-1, rounded half-up) or src[b] itself when the stretch is off.
+ * params: f64 [B, 4] on the DEVICE, per image (kx, ky, shift, flags), flags bit 0 = stretch, bit 1 = flip; shift is taken modulo W
+ * (a captured graph replays with whatever the buffer holds).  src, dst: uint8 [B, H, W, C], distinct; H >= 2, W even, 1 <= C <= 4. */
+int pswin_pano_warp_u8(const uint8_t* src, const double* params, uint8_t* dst, int B, int H, int W, int C, void* stream);
+
+/* Resize(keep_ratio) + Normalize + Pad + collate of the recipe, into the backbone's input:
+ *   dst[b][c][y][x] = (u - norm[c]) * norm[3 + c] for y < out_hw[b][0], x < out_hw[b][1], else 0 (the pad, written here),
+ *   u = floor(bilinear(src[b], channel to_rgb ? 2-c : c) + 0.5), the bilinear resize from H x W to out_hw[b] in float32 with
+ *   src = (dst + 0.5) * (in / out) - 0.5 clamped at 0 and the last row / column replicated (cv2 INTER_LINEAR geometry).
+ * src: uint8 [B, H, W, 3]; out_hw: int32 [B, 2] on the DEVICE (clamped to [0, Hp] x [0, Wp]); norm: f32 [6] on the device = the
+ * mean and 1/std of each OUTPUT channel; dst: f32 [B, 3, Hp, Wp]. */
+int pswin_pano_resize_normalize_pad(const uint8_t* src, const int32_t* out_hw, const float* norm, int to_rgb, float* dst, int B, int H,
+                                    int W, int Hp, int Wp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

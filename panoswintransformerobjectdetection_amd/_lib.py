@@ -125,6 +125,8 @@ _PROTOTYPES = {
                           _i, _i, _i, _i, _f, _i, _vp],
     "pswin_attn_table_grads_workspace": [_i],
     "pswin_attn_table_grads": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "pswin_pano_warp_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "pswin_pano_resize_normalize_pad": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
 }
 
 _lib = None

@@ -1,0 +1,374 @@
+"""PanoSwin's panorama training augmentation on the device: PanoStretch, RollAug, RandomFlip, Resize, Normalize and Pad.
+
+The reference runs these in its CPU data pipeline (configs/swin/faster_rcnn_panoswin_tiny_patch4_window7_mstrain_480800_adamw_1x_
+streetwin.py:62-66; PanoStretch and RollAug at mmdet/datasets/pipelines/transforms.py:992-1068, which call
+lzx/yolo/extensions/xzaug.py getAug / _xzaug, rollaug.py roll_aug_raw and padding2.py merge_adjbox).  Here the pixels go through two
+HIP kernels (csrc/pswin_pano.hip) and the boxes stay on the host in numpy, with the reference's dtypes, order and rounding.
+
+Image contract: the warp (stretch, roll, flip) is byte-identical to the reference.  For output pixel (x, y) of an H x W image
+(W even: sin u = 0 at x = (W-1)/2 otherwise) the stretch samples the source at (refy, refx), in float64 and in this order:
+
+    u  = ((x+0.5)/W - 0.5)*2*pi            v  = ((y+0.5)/H - 0.5)*pi
+    u0 = atan2(sin u * kx / ky, cos u)     v0 = atan(tan v * sin u0 / sin u * ky)
+    refx = (u0/(2*pi) + 0.5)*W - 0.5       refy = (v0/pi + 0.5)*H - 0.5
+
+Quirks that are part of the contract:
+  * scipy's map_coordinates(order=1, mode='wrap') is not a periodic wrap: the period is n-1 and the first and last samples coincide,
+    along both axes.  Wherever refy < 0 the top row blends rows H-2 and H-1; wherever refx < 0 column 0 blends columns W-2 and W-1.
+    The weights are w0 = 1 - t and w1 = 1 - w0, the taps accumulate row-major as (value * wy) * wx, and the sum is rounded half-up
+    and clamped to uint8 (1.5 -> 2, 2.5 -> 3).
+  * with kx == ky the columns 0 and W-1 sit on that seam (refx = 0 or W-1 up to the last bit of atan2), so which side of the seam
+    they sample depends on how the platform's atan2 rounds; random draws never give kx == ky.
+  * a stretch that is not drawn copies the image; roll_dist = (int(r*100000) % 100000) / 100000, shift = int(roll_dist*W),
+    out[:, x] = in[:, (x - shift) mod W] (np.roll); the flip is out[:, x] = in[:, W-1-x] (mmcv.imflip, horizontal).
+
+Boxes (transform_boxes), in the reference's order and precision:
+  1. PanoStretch: both corners through the inverse map u' = atan2(sin u0 * ky/kx, cos u0), v' = atan(tan v0 * sin u' / sin u0 / ky),
+     then np.round.  A corner at x = W wraps: at W = 128, kx = 1.7, ky = 0.6 the box [100, 20, 128, 40] gets x2 = -0.32 before
+     rounding.  Labels pass through float64 and are rounded back to int64.
+  2. RollAug: normalise by (W, H), add roll_dist to x1 and x2; a box with x2 > 1 whose centre is past 1 moves back by 1 (with clip01
+     x1 is clamped at 0), otherwise, with clip01, x2 = 1.  Then merge_adjbox: every box with x1 == roll_dist is paired with every box
+     with x2 == roll_dist (eps 1e-9), a cross product; the merged row is the second box's row (label and y included) with x2 of the
+     first, and that row is modified in place, so a row merged twice shows the last partner's x2 everywhere it was emitted.
+     Un-normalise, np.round.
+  3. RandomFlip: x1' = W - x2, x2' = W - x1.
+A batch image without boxes stays without boxes (the reference's RollAug raises on an empty box array).
+
+Random draws per image, in the reference's order: rand() < stretch_chance, uniform(1, kxy[0]), uniform(1, kxy[1]), rand() < 0.5
+(kx = 1/kx), rand() < 0.5 (ky = 1/ky); rand() < roll_chance, rand() for roll_dist; choice(['horizontal', None], p=[r, 1-r]);
+PanoTrainTransform then draws the Resize scale with randint(len(img_scales)).  Seeded, one image after the other, this reproduces
+the reference pipeline for a recipe without AutoAugment.
+
+Resize, Normalize, Pad (pswin_pano_resize_normalize_pad): mmdet Resize(keep_ratio=True) with one scale per image
+(sf = min(max(scale)/max(h, w), min(scale)/min(h, w)), new size int(w*sf + 0.5) x int(h*sf + 0.5), boxes times (new_w/w, new_h/h)
+in float32 and clipped); the pixels are resampled bilinearly with the geometry of cv2 INTER_LINEAR (src = (dst+0.5)*(in/out) - 0.5,
+border replicated) in float32 and rounded half-up.  This is NOT bit-exact to cv2, which rounds with fixed-point weights: the resized
+uint8 image may differ from mmcv.imresize by 1 LSB.  Normalize is mmcv.imnormalize: BGR -> RGB, then (v - mean) * (1/std) in float32
+(mean and 1/std rounded to float32 first, as cv2 does with the scalar).  Pad writes zeros up to a multiple of size_divisor and to
+the largest image of the batch (mmdet Pad followed by collate).
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import PswinError
+
+STRETCH, FLIP = 1, 2
+
+# streetwin config (configs/swin/faster_rcnn_panoswin_tiny_patch4_window7_mstrain_480800_adamw_1x_streetwin.py:47-58)
+TRAIN_RESIZE_SCALES = [(480, 1333), (512, 1333), (544, 1333), (576, 1333), (608, 1333), (640, 1333), (672, 1333), (704, 1333),
+                       (736, 1333), (768, 1333), (800, 1333)]
+IMG_NORM_MEAN = (123.675, 116.28, 103.53)
+IMG_NORM_STD = (58.395, 57.12, 57.375)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# random draws
+# ------------------------------------------------------------------------------------------------------------------------------
+
+def draw_pano_params(batch, W, kxy=(2., 2.), stretch_chance=1., roll_chance=1., flip_ratio=.5, rng=np.random):
+    """Draw PanoStretch, RollAug and RandomFlip parameters for `batch` images of width W, image after image, in the reference's order.
+
+    Returns a dict of host arrays of length `batch`: stretch (bool), kx, ky (float64, 1 when not stretched), roll (bool), roll_dist
+    (float64, 0 when not rolled), shift (int64), flip (bool).  rng: np.random or a np.random.RandomState."""
+    p = dict(stretch=np.zeros(batch, bool), kx=np.ones(batch), ky=np.ones(batch), roll=np.zeros(batch, bool),
+             roll_dist=np.zeros(batch), shift=np.zeros(batch, np.int64), flip=np.zeros(batch, bool))
+    for i in range(batch):
+        if rng.rand() < stretch_chance:
+            kx = rng.uniform(1.0, kxy[0])
+            ky = rng.uniform(1.0, kxy[1])
+            if rng.rand() < 0.5:
+                kx = 1.0 / kx
+            if rng.rand() < 0.5:
+                ky = 1.0 / ky
+            p["stretch"][i], p["kx"][i], p["ky"][i] = True, kx, ky
+        if rng.rand() < roll_chance:
+            roll_dist = (int(rng.rand() * 100000) % 100000) / 100000
+            p["roll"][i], p["roll_dist"][i], p["shift"][i] = True, roll_dist, int(roll_dist * W)
+        if flip_ratio is not None:
+            p["flip"][i] = rng.choice(2, p=[flip_ratio, 1 - flip_ratio]) == 0
+    return p
+
+
+def make_pano_params(stretch, kx, ky, roll_dist, flip, W):
+    """Parameters of one or more images from explicit values (roll_dist None: no roll), in the layout draw_pano_params returns."""
+    stretch, kx, ky, flip = (np.atleast_1d(np.asarray(a)) for a in (stretch, kx, ky, flip))
+    n = len(stretch)
+    rd = [None] * n if roll_dist is None else list(np.atleast_1d(np.asarray(roll_dist, dtype=object)))
+    roll = np.array([r is not None for r in rd])
+    dist = np.array([0.0 if r is None else (int(float(r) * 100000) % 100000) / 100000 for r in rd])
+    return dict(stretch=stretch.astype(bool), kx=np.where(stretch, kx, 1.0).astype(np.float64),
+                ky=np.where(stretch, ky, 1.0).astype(np.float64), roll=roll, roll_dist=dist,
+                shift=np.array([int(d * W) for d in dist], np.int64), flip=flip.astype(bool))
+
+
+def params_array(params):
+    """Host float64 [B, 4] (kx, ky, shift, flags) of pswin_pano_warp_u8."""
+    flags = params["stretch"].astype(np.int64) * STRETCH + params["flip"].astype(np.int64) * FLIP
+    return np.stack([params["kx"], params["ky"], params["shift"].astype(np.float64), flags.astype(np.float64)], 1)
+
+
+def params_tensor(params, device):
+    return torch.from_numpy(params_array(params)).to(device=device, dtype=torch.float64)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# kernels
+# ------------------------------------------------------------------------------------------------------------------------------
+
+def _check_images(imgs, what, channels=None):
+    if not isinstance(imgs, torch.Tensor) or not imgs.is_cuda:
+        raise PswinError(f"{what}: the PanoSwin kernels run on an MI355X (HIP) device only; got a CPU tensor")
+    if imgs.dtype != torch.uint8 or imgs.dim() != 4:
+        raise PswinError(f"{what}: expected uint8 [B, H, W, C] images, got {imgs.dtype} {tuple(imgs.shape)}")
+    if channels is not None and imgs.shape[3] not in channels:
+        raise PswinError(f"{what}: expected {channels} channels, got {imgs.shape[3]}")
+
+
+def _overlaps(a, b):
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _check_buffer(t, what, name, dtype, shape, device, inputs=()):
+    """A caller-supplied buffer the kernel writes (or reads) by raw pointer: it must be exactly what the launch assumes."""
+    if not isinstance(t, torch.Tensor) or t.device != device or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}, contiguous={t.is_contiguous()}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise PswinError(f"{what}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}; got {got}")
+    for other in inputs:
+        if _overlaps(t, other):
+            raise PswinError(f"{what}: {name} must not overlap an input of the launch")
+
+
+def pano_warp(imgs_u8, params, out=None):
+    """Stretch, roll and flip a batch of uint8 [B, H, W, C] panoramas on the device in one pass.
+
+    params: the dict of draw_pano_params / make_pano_params, or a device float64 [B, 4] tensor (kx, ky, shift, flags) -- the form a
+    captured graph replays after new values are copied into it."""
+    _check_images(imgs_u8, "pano_warp", (1, 2, 3, 4))
+    B, H, W, C = imgs_u8.shape
+    if W % 2:
+        raise PswinError(f"pano_warp: the width must be even (sin u = 0 at x = (W-1)/2), got {W}")
+    if H < 2:
+        raise PswinError(f"pano_warp: the height must be at least 2, got {H}")
+    if isinstance(params, dict):
+        params = params_tensor(params, imgs_u8.device)
+    if params.dtype != torch.float64 or tuple(params.shape) != (B, 4) or params.device != imgs_u8.device or not params.is_contiguous():
+        raise PswinError("pano_warp: params must be a contiguous float64 [B, 4] tensor on the images' device")
+    x = imgs_u8.contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _check_buffer(out, "pano_warp", "out", torch.uint8, (B, H, W, C), x.device, (x, params))
+    _lib.call("pswin_pano_warp_u8", x, _lib.ptr(x), _lib.ptr(params), _lib.ptr(out), B, H, W, C, algo_bytes=2 * x.numel())
+    return out
+
+
+def norm_tensor(mean, std, device):
+    """f32 [6] (mean, 1/std) per output channel: both rounded to float32 as cv2 rounds the scalars of mmcv.imnormalize."""
+    mean = np.asarray(mean, np.float64).reshape(3)
+    inv = 1.0 / np.asarray(std, np.float64).reshape(3)
+    return torch.tensor(np.concatenate([mean, inv]).astype(np.float32), device=device)
+
+
+def padded_size(sizes, size_divisor):
+    d = max(1, int(size_divisor or 1))
+    return (-(-max(h for h, _ in sizes) // d) * d, -(-max(w for _, w in sizes) // d) * d)
+
+
+def resize_normalize_pad(imgs_u8, out_hw, mean=IMG_NORM_MEAN, std=IMG_NORM_STD, to_rgb=True, size_divisor=32, pad_hw=None, out=None,
+                         norm=None):
+    """Resize every uint8 [H, W, 3] image of the batch to its own out_hw[b] = (h, w), normalise and zero-pad into float32
+    [B, 3, Hp, Wp].  out_hw: host list of (h, w), or a device int32 [B, 2] tensor (then pad_hw = (Hp, Wp) must be given: the
+    padded size fixes the launch).  Hp, Wp default to the batch maximum rounded up to size_divisor."""
+    _check_images(imgs_u8, "resize_normalize_pad", (3,))
+    B, H, W, _ = imgs_u8.shape
+    dev = imgs_u8.device
+    if isinstance(out_hw, torch.Tensor):
+        if pad_hw is None:
+            raise PswinError("resize_normalize_pad: pass pad_hw with a device out_hw tensor")
+        if out_hw.dtype != torch.int32 or tuple(out_hw.shape) != (B, 2) or out_hw.device != dev or not out_hw.is_contiguous():
+            raise PswinError("resize_normalize_pad: out_hw must be a contiguous int32 [B, 2] tensor on the images' device")
+        hw_t = out_hw
+    else:
+        sizes = [(int(h), int(w)) for h, w in out_hw]
+        if len(sizes) != B or min(min(s) for s in sizes) < 1:
+            raise PswinError(f"resize_normalize_pad: need {B} positive output sizes, got {sizes}")
+        if pad_hw is None:
+            pad_hw = padded_size(sizes, size_divisor)
+        if any(h > pad_hw[0] or w > pad_hw[1] for h, w in sizes):
+            raise PswinError(f"resize_normalize_pad: an output size exceeds the padded size {pad_hw}")
+        hw_t = torch.tensor(sizes, dtype=torch.int32, device=dev)
+    Hp, Wp = int(pad_hw[0]), int(pad_hw[1])
+    if Hp < 1 or Wp < 1:
+        raise PswinError(f"resize_normalize_pad: the padded size must be positive, got {pad_hw}")
+    if norm is None:
+        norm = norm_tensor(mean, std, dev)
+    else:
+        _check_buffer(norm, "resize_normalize_pad", "norm", torch.float32, (6,), dev)
+    x = imgs_u8.contiguous()
+    if out is None:
+        out = torch.empty(B, 3, Hp, Wp, device=dev, dtype=torch.float32)
+    else:
+        _check_buffer(out, "resize_normalize_pad", "out", torch.float32, (B, 3, Hp, Wp), dev, (x, hw_t, norm))
+    _lib.call("pswin_pano_resize_normalize_pad", x, _lib.ptr(x), _lib.ptr(hw_t), _lib.ptr(norm), int(bool(to_rgb)), _lib.ptr(out), B, H,
+              W, Hp, Wp, algo_bytes=x.numel() + out.numel() * 4)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# boxes (host, numpy)
+# ------------------------------------------------------------------------------------------------------------------------------
+
+def _stretch_corners(pts, H, W, kx, ky):
+    u0 = ((pts[:, 0] + 0.5) / W - 0.5) * 2 * np.pi
+    v0 = ((pts[:, 1] + 0.5) / H - 0.5) * np.pi
+    u = np.arctan2(np.sin(u0) * ky / kx, np.cos(u0))
+    v = np.arctan(np.tan(v0) * np.sin(u) / np.sin(u0) / ky)
+    return np.stack([(u / (2 * np.pi) + 0.5) * W - 0.5, (v / np.pi + 0.5) * H - 0.5], axis=-1)
+
+
+def _roll_rows(rows, roll_dist, clip01, eps=1e-9):
+    """rows: float64 [n, 5] (label, x1, y1, x2, y2) normalised.  Shifts x by roll_dist, applies the wrap rule and the seam merge of
+    the module docstring (RollAug step 2) and returns the new rows; `rows` is modified."""
+    x1, x2 = rows[:, 1], rows[:, 3]
+    x1 += roll_dist
+    x2 += roll_dist
+    # wrap rule, per box: past the seam with its centre -> back by one period; past it with the centre inside -> cut (clip01)
+    past = x2 > 1.0
+    back = past & ((x2 + x1) / 2 > 1.0)
+    x2[back] -= 1.0
+    x1[back] = np.maximum(x1[back] - 1.0, 0.0) if clip01 else x1[back] - 1.0
+    if clip01:
+        x2[past & ~back] = 1.0
+    # seam merge.  Left pieces start at roll_dist, right pieces end there.  Every (left, right) pair is visited in the order of
+    # Python's set iteration over the indices (the reference collects them in sets); the right row takes the left row's x2 in
+    # place, so a right row paired several times ends with its last partner's x2, and every emitted copy shows that final state.
+    left = list(set(np.flatnonzero(np.abs(x1 - roll_dist) < eps).tolist()))
+    right = list(set(np.flatnonzero(np.abs(x2 - roll_dist) < eps).tolist()))
+    if not left or not right:
+        return rows.copy()
+    emitted = []
+    for i in left:
+        for j in right:
+            rows[j, 3] = rows[i, 3]
+            emitted.append(j)
+    paired = set(left) | set(right)
+    emitted += [i for i in range(len(rows)) if i not in paired]
+    return rows[emitted]
+
+
+def transform_one(boxes, labels, H, W, stretch, kx, ky, roll, roll_dist, flip, clip01=True):
+    """One image's boxes (float32 [n, 4] x1 y1 x2 y2 pixels) and labels (int64 [n]) through PanoStretch, RollAug and RandomFlip."""
+    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+    labels = np.asarray(labels, np.int64).reshape(-1)
+    if len(boxes) != len(labels):
+        raise PswinError(f"transform_boxes: {len(boxes)} boxes but {len(labels)} labels")
+    if len(boxes) == 0:
+        return boxes.copy(), labels.copy()
+    if stretch:
+        rows = np.concatenate([labels[:, None], boxes], 1)                       # float64, as the reference's concatenate
+        pts = _stretch_corners(rows[:, 1:].copy().reshape(-1, 2), H, W, kx, ky).reshape(-1, 4)
+        labels = np.round(rows[:, 0]).astype(np.int64)
+        boxes = np.round(pts).astype(np.float32)
+    if roll:
+        xyxy = boxes.astype(np.float64)
+        xyxy[:, [0, 2]] /= W
+        xyxy[:, [1, 3]] /= H
+        rows = _roll_rows(np.concatenate([labels[:, None], xyxy], 1), roll_dist, clip01)
+        labels = np.round(rows[:, 0]).astype(np.int64)
+        xyxy = rows[:, 1:]
+        xyxy[:, [0, 2]] *= W
+        xyxy[:, [1, 3]] *= H
+        boxes = np.round(xyxy).astype(np.float32)
+    if flip:
+        f = boxes.copy()
+        f[:, 0] = W - boxes[:, 2]
+        f[:, 2] = W - boxes[:, 0]
+        boxes = f
+    return boxes, labels
+
+
+def transform_boxes(boxes, labels, H, W, params, clip01=True):
+    """Lists of per-image boxes and labels through PanoStretch, RollAug and RandomFlip with the drawn `params`."""
+    if len(boxes) != len(params["stretch"]) or len(labels) != len(boxes):
+        raise PswinError("transform_boxes: one boxes and one labels array per image of params")
+    out_b, out_l = [], []
+    for i in range(len(boxes)):
+        b, l = transform_one(boxes[i], labels[i], H, W, params["stretch"][i], params["kx"][i], params["ky"][i], params["roll"][i],
+                             params["roll_dist"][i], params["flip"][i], clip01)
+        out_b.append(b)
+        out_l.append(l)
+    return out_b, out_l
+
+
+def rescale_size(h, w, scale):
+    """(new_h, new_w) of mmcv.rescale_size((w, h), scale) for a (long, short) or (short, long) scale tuple."""
+    sf = min(max(scale) / max(h, w), min(scale) / min(h, w))
+    return int(h * float(sf) + 0.5), int(w * float(sf) + 0.5)
+
+
+def resize_boxes(boxes, h, w, new_h, new_w):
+    """mmdet Resize._resize_bboxes: float32 boxes times (new_w/w, new_h/h), clipped to the new image."""
+    sf = np.array([new_w / w, new_h / h, new_w / w, new_h / h], dtype=np.float32)
+    b = np.asarray(boxes, np.float32).reshape(-1, 4) * sf
+    b[:, 0::2] = np.clip(b[:, 0::2], 0, new_w)
+    b[:, 1::2] = np.clip(b[:, 1::2], 0, new_h)
+    return b
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the recipe
+# ------------------------------------------------------------------------------------------------------------------------------
+
+class PanoTrainTransform:
+    """PanoStretch -> RollAug -> RandomFlip -> Resize -> Normalize -> Pad of the streetwin recipe, pixels on the device.
+
+        x, boxes, labels, img_metas = PanoTrainTransform()(imgs_u8, boxes, labels)
+
+    imgs_u8: uint8 [B, H, W, 3] BGR on the device, all of one size (group mixed sizes into separate calls); boxes: list of float32
+    [n_i, 4]; labels: list of int64 [n_i].  x: float32 [B, 3, Hp, Wp], the backbone's input."""
+
+    def __init__(self, kxy=(2.0, 2.0), stretch_chance=1.0, roll_chance=1.0, clip01=True, flip_ratio=0.5, img_scales=TRAIN_RESIZE_SCALES,
+                 mean=IMG_NORM_MEAN, std=IMG_NORM_STD, to_rgb=True, size_divisor=32, rng=np.random):
+        self.kxy, self.stretch_chance, self.roll_chance, self.clip01 = tuple(kxy), stretch_chance, roll_chance, clip01
+        self.flip_ratio, self.img_scales = flip_ratio, [tuple(s) for s in img_scales]
+        self.mean, self.std, self.to_rgb, self.size_divisor, self.rng = mean, std, to_rgb, size_divisor, rng
+        self._norm = {}
+
+    def draw(self, B, W):
+        """Per image: the pano parameters, then the Resize scale (the reference's order)."""
+        parts, scales = [], []
+        for _ in range(B):
+            parts.append(draw_pano_params(1, W, self.kxy, self.stretch_chance, self.roll_chance, self.flip_ratio, self.rng))
+            scales.append(self.img_scales[self.rng.randint(len(self.img_scales))] if len(self.img_scales) > 1 else self.img_scales[0])
+        params = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        return params, scales
+
+    def __call__(self, imgs_u8, boxes, labels):
+        _check_images(imgs_u8, "PanoTrainTransform", (3,))
+        B, H, W, _ = imgs_u8.shape
+        if len(boxes) != B or len(labels) != B:
+            raise PswinError(f"PanoTrainTransform: {B} images but {len(boxes)} box arrays and {len(labels)} label arrays")
+        params, scales = self.draw(B, W)
+        sizes = [rescale_size(H, W, s) for s in scales]
+        pad_hw = padded_size(sizes, self.size_divisor)
+        dev = imgs_u8.device
+        if dev not in self._norm:
+            self._norm[dev] = norm_tensor(self.mean, self.std, dev)
+        warped = pano_warp(imgs_u8, params)
+        x = resize_normalize_pad(warped, sizes, to_rgb=self.to_rgb, size_divisor=self.size_divisor, pad_hw=pad_hw, norm=self._norm[dev])
+        boxes, labels = transform_boxes(boxes, labels, H, W, params, self.clip01)
+        metas = []
+        for i, (nh, nw) in enumerate(sizes):
+            boxes[i] = resize_boxes(boxes[i], H, W, nh, nw)
+            d = self.size_divisor or 1
+            metas.append(dict(ori_shape=(H, W, 3), img_shape=(nh, nw, 3), pad_shape=(-(-nh // d) * d, -(-nw // d) * d, 3),
+                              batch_input_shape=tuple(pad_hw), scale=scales[i],
+                              scale_factor=np.array([nw / W, nh / H, nw / W, nh / H], np.float32),
+                              flip=bool(params["flip"][i]), flip_direction="horizontal" if params["flip"][i] else None,
+                              pano_stretch=(float(params["kx"][i]), float(params["ky"][i])) if params["stretch"][i] else None,
+                              roll_dist=float(params["roll_dist"][i]) if params["roll"][i] else None, roll_shift=int(params["shift"][i]),
+                              img_norm_cfg=dict(mean=np.array(self.mean, np.float32), std=np.array(self.std, np.float32),
+                                                to_rgb=self.to_rgb)))
+        return x, boxes, labels, metas
