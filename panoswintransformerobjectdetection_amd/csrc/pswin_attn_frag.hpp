@@ -219,7 +219,9 @@ __device__ inline void store_quad(void* base, size_t off, f32x4 q) {
     store4<DT>(base, off, q);
 }
 
-__device__ inline void swap16_u32(unsigned& a, unsigned& b) { asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
+// swap16_u32 (pswin_common.hpp) as inline asm, kept for the attention stores: the builtin makes the compiler reschedule the
+// attention kernels, a change that wants a GPU measurement of its own.  The operands are VALU conversions, which the s_nop covers.
+__device__ inline void swap16_u32_asm(unsigned& a, unsigned& b) { asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
 
 // A lane (c, g) holds, for one output row, the head-dim quads q0 = d[4g .. 4g+3] and q1 = d[16+4g .. 16+4g+3] (the two
 // 16-wide MFMA tiles).  Exchanging q1 of the even groups with q0 of the odd groups (lanes 16 apart: one
@@ -229,11 +231,11 @@ __device__ inline void swap16_u32(unsigned& a, unsigned& b) { asm volatile("s_no
 // row_boff: byte offset of the lane's row within the window's head slice (see window_rsrc).
 template <int DT>
 __device__ inline void store_row8_at(rsrc_t rs, unsigned row_boff, int g, f32x4 q0, f32x4 q1) {
-    const int d0 = 8 * (g >> 1) + 16 * (g & 1);
+    const int d0 = row8_d0(g);
     if constexpr (DT == PSWIN_BF16) {
         unsigned a0 = pack2_bf16(q0[0], q0[1]), a1 = pack2_bf16(q0[2], q0[3]), b0 = pack2_bf16(q1[0], q1[1]), b1 = pack2_bf16(q1[2], q1[3]);
-        swap16_u32(a0, b0);
-        swap16_u32(a1, b1);
+        swap16_u32_asm(a0, b0);
+        swap16_u32_asm(a1, b1);
         const u32x4 v = {a0, a1, b0, b1};
         __builtin_amdgcn_raw_buffer_store_b128(v, rs, row_boff + (unsigned)d0 * 2u, 0, 0);
     } else {
@@ -267,16 +269,6 @@ __device__ inline float group_sum(float v) {
     b = a;
     swap32(a, b);
     return a + b;
-}
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ inline float row16_sum(float v) {   // across the 16 lanes of a group: quad xor 1, xor 2, then mirrors
-    v = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
-    v = dpp_add<0x141>(v);   // row_half_mirror: the other quad of the 8 (all 4 lanes of a quad agree by now)
-    return dpp_add<0x140>(v);   // row_mirror: the other half of the 16
 }
 
 constexpr int NBINS = (2 * PSWIN_WS - 1) * (2 * PSWIN_WS - 1);   // 169

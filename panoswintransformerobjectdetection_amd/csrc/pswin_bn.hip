@@ -20,41 +20,6 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int MAX_BLOCKS = 1024;
 
-template <int DT>
-struct Vec {
-    static constexpr int VE = (DT == PSWIN_BF16) ? 8 : 4;
-};
-
-template <int DT>
-__device__ inline void load_vec(const void* base, size_t elem_off, float (&v)[Vec<DT>::VE]) {
-    if constexpr (DT == PSWIN_BF16) {
-        const u32x4 raw = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(base) + elem_off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[2 * e] = __builtin_bit_cast(float, raw[e] << 16);
-            v[2 * e + 1] = __builtin_bit_cast(float, raw[e] & 0xffff0000u);
-        }
-    } else {
-        const f32x4 r = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + elem_off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = r[e];
-    }
-}
-
-template <int DT>
-__device__ inline void store_vec(void* base, size_t elem_off, const float (&v)[Vec<DT>::VE]) {
-    if constexpr (DT == PSWIN_BF16) {
-        u32x4 raw;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            raw[e] = pack2_bf16(v[2 * e], v[2 * e + 1]);
-        *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(base) + elem_off) = raw;
-    } else {
-        f32x4 r = {v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(base) + elem_off) = r;
-    }
-}
-
 // Two per-channel sums over the rows.  MODE 0 (forward stats): (sum y, sum y^2).
 // MODE 1 (backward): g = dz * [relu input > 0]; (sum g, sum g * xhat).   partial: [gridDim.x][2][C]
 template <int DT, int MODE>

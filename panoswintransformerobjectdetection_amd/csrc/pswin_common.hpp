@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "pswin.h"
 
@@ -74,6 +75,96 @@ __device__ inline void store4(void* base, size_t elem_off, f32x4 v) {
     }
 }
 
+// One 16-byte channel group of a row as f32: 8 bf16 or 4 f32 elements
+template <int DT>
+struct Vec {
+    static constexpr int VE = (DT == PSWIN_BF16) ? 8 : 4;
+};
+
+template <int DT>
+__device__ inline void load_vec(const void* base, size_t elem_off, float (&v)[Vec<DT>::VE]) {
+    if constexpr (DT == PSWIN_BF16) {
+        const u32x4 raw = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(base) + elem_off);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[2 * e] = __builtin_bit_cast(float, raw[e] << 16);
+            v[2 * e + 1] = __builtin_bit_cast(float, raw[e] & 0xffff0000u);
+        }
+    } else {
+        const f32x4 r = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + elem_off);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = r[e];
+    }
+}
+
+template <int DT>
+__device__ inline void store_vec(void* base, size_t elem_off, const float (&v)[Vec<DT>::VE]) {
+    if constexpr (DT == PSWIN_BF16) {
+        u32x4 raw;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            raw[e] = pack2_bf16(v[2 * e], v[2 * e + 1]);
+        *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(base) + elem_off) = raw;
+    } else {
+        f32x4 r = {v[0], v[1], v[2], v[3]};
+        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(base) + elem_off) = r;
+    }
+}
+
+// v_mfma_f32_16x16x32_bf16 on 8-element bf16 operand fragments (or their 4 packed dwords)
+__device__ inline f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+__device__ inline f32x4 mfma32(u32x4 a, u32x4 b, f32x4 c) {
+    return mfma32(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c);
+}
+
+// v plus the value of the lane that DPP control CTRL selects within its 16-lane row: one v_add_f32 with a DPP modifier
+template <int CTRL>
+__device__ inline float dpp_add(float v) {
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+__device__ inline float row16_sum(float v) {   // across the 16 lanes of a group (every lane gets the sum)
+    v = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
+    v = dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
+    v = dpp_add<0x141>(v);   // row_half_mirror: the other quad of the 8 (all 4 lanes of a quad agree by now)
+    return dpp_add<0x140>(v);   // row_mirror: the other half of the 16
+}
+
+// v_permlane16_swap: exchanges the odd 16-lane rows of a with the even rows of b.  The builtin (not inline asm) so that
+// the compiler's hazard recognizer sees the instruction: its operands often come straight from MFMA accumulators, and
+// the MFMA-write -> VALU-read wait states are software managed (an asm version with a fixed s_nop read stale values).
+__device__ inline void swap16_u32(unsigned& a, unsigned& b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    a = r[0];
+    b = r[1];
+}
+
+// Rows of two 16-wide MFMA tiles.  Lane (c, g) holds, for one row, the accumulator quads q0 = col[4g..4g+3] and
+// q1 = col[16+4g..16+4g+3] of a 32-column group.  Exchanging q1 of the even groups with q0 of the odd ones (lanes 16 apart)
+// leaves every lane with 8 CONTIGUOUS columns starting at row8_d0(g): one 16-byte row store instead of two 8-byte ones.
+__device__ inline int row8_d0(int g) { return 8 * (g >> 1) + 16 * (g & 1); }
+// the two quads as the 8-element operand fragment {q0[0..3], q1[0..3]} of bf16 pairs
+__device__ inline u32x4 pack8(f32x4 q0, f32x4 q1) {
+    return u32x4{pack2_bf16(q0[0], q0[1]), pack2_bf16(q0[2], q0[3]), pack2_bf16(q1[0], q1[1]), pack2_bf16(q1[2], q1[3])};
+}
+// a packed fragment -> this lane's 8 contiguous columns
+__device__ inline u32x4 row8(u32x4 f) {
+    const auto r0 = __builtin_amdgcn_permlane16_swap(f[0], f[2], false, false);
+    const auto r1 = __builtin_amdgcn_permlane16_swap(f[1], f[3], false, false);
+    return u32x4{r0[0], r1[0], r0[1], r1[1]};
+}
+__device__ inline u32x4 pack_row8(f32x4 q0, f32x4 q1) { return row8(pack8(q0, q1)); }
+// the same exchange on f32 quads.  Whole-vector bit casts only: hipcc (ROCm 7.2) folds __builtin_bit_cast(T, vec[e])
+// inside an unrolled loop to element 0.
+__device__ inline void exchange_row8(f32x4& q0, f32x4& q1) {
+    const u32x4 a = __builtin_bit_cast(u32x4, q0), b = __builtin_bit_cast(u32x4, q1);
+    const auto r0 = __builtin_amdgcn_permlane16_swap(a[0], b[0], false, false);
+    const auto r1 = __builtin_amdgcn_permlane16_swap(a[1], b[1], false, false);
+    const auto r2 = __builtin_amdgcn_permlane16_swap(a[2], b[2], false, false);
+    const auto r3 = __builtin_amdgcn_permlane16_swap(a[3], b[3], false, false);
+    q0 = __builtin_bit_cast(f32x4, u32x4{r0[0], r1[0], r2[0], r3[0]});
+    q1 = __builtin_bit_cast(f32x4, u32x4{r0[1], r1[1], r2[1], r3[1]});
+}
+
 // out[c] = sum_r part[r][c] (r in fixed order: bitwise reproducible).  16 columns x 64 row lanes per block, so that
 // even 512 partial rows are only 8 (independent) loads deep per thread: this stage is pure latency.
 __global__ static void colsum_kernel(const float* __restrict__ part, int R, int N, float* __restrict__ out) {
@@ -128,5 +219,14 @@ inline int ensure_dynamic_lds(const void* kernel, size_t bytes, std::atomic<unsi
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool valid_dtype(int dt) { return dt == PSWIN_F32 || dt == PSWIN_BF16; }
+
+// f(std::integral_constant a, std::integral_constant b) for two dtypes that passed valid_dtype
+template <typename F>
+inline int dispatch2(int a, int b, F&& f) {
+    if (a == PSWIN_F32 && b == PSWIN_F32) return f(std::integral_constant<int, PSWIN_F32>(), std::integral_constant<int, PSWIN_F32>());
+    if (a == PSWIN_F32 && b == PSWIN_BF16) return f(std::integral_constant<int, PSWIN_F32>(), std::integral_constant<int, PSWIN_BF16>());
+    if (a == PSWIN_BF16 && b == PSWIN_F32) return f(std::integral_constant<int, PSWIN_BF16>(), std::integral_constant<int, PSWIN_F32>());
+    return f(std::integral_constant<int, PSWIN_BF16>(), std::integral_constant<int, PSWIN_BF16>());
+}
 
 }  // namespace pswin

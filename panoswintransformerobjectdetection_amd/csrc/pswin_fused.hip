@@ -69,22 +69,6 @@ struct FusedArgs {
 __device__ inline int woff(int row, int chunk) { return row * 192 + (((chunk & ~3) | ((chunk ^ (row >> 1)) & 3)) << 4); }
 __device__ inline int bias_off(int h, int i, int q) { return ((h * TOK + i) * 16 + ((q + 2 * i) & 15)) * 16; }   // bytes
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-// one v_cvt_pk_bf16_f32 (the scalar cast + shift + or form costs 2 conversions and 2 integer ops per pair)
-__device__ inline unsigned pk(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2)); }
-// two accumulator quads (elements 4g+e of two 16-wide tiles) -> the 8-element operand fragment {lo[0..3], hi[0..3]}
-__device__ inline u32x4 pack8(f32x4 lo, f32x4 hi) { return u32x4{pk(lo[0], lo[1]), pk(lo[2], lo[3]), pk(hi[0], hi[1]), pk(hi[2], hi[3])}; }
-// the same 8 values of this lane and of the lane 16 away re-grouped into 8 CONTIGUOUS columns starting at
-// 8 (g >> 1) + 16 (g & 1) of the 32-column group (one 16-byte row store instead of two 8-byte ones)
-__device__ inline u32x4 row8(u32x4 f) {
-    const auto r0 = __builtin_amdgcn_permlane16_swap(f[0], f[2], false, false);     // the builtin: hipcc pads the hazard only where needed
-    const auto r1 = __builtin_amdgcn_permlane16_swap(f[1], f[3], false, false);
-    return u32x4{r0[0], r1[0], r0[1], r1[1]};
-}
-__device__ inline f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 #ifdef PSWIN_FUSED_CLOCK_PROBE
 __device__ unsigned long long pswin_fused_clock_probe[256][2];
 #endif
@@ -123,7 +107,7 @@ __global__ __launch_bounds__(FTHREADS, 2) void win_fused_fwd_kernel(FusedArgs a)
     }
     const float inv_scale = 1.0f / a.scale;
     const float sl2e = a.scale * LOG2E;
-    const int d0 = 8 * (g >> 1) + 16 * (g & 1);       // first of this lane's 8 contiguous columns after row8()
+    const int d0 = row8_d0(g);   // first of this lane's 8 contiguous columns after row8()
     // LDS addresses as ONE per-lane base + compile-time offsets (ds_read offset field), instead of one hoisted VGPR per
     // (row block, step): for row blocks that start at a multiple of 8, woff(R + c, 4 s + g) = R * 192 + 64 s + wlane
     const char* wq_l = wq + c * 192 + (((g ^ (c >> 1)) & 3) << 4);
@@ -227,7 +211,7 @@ __global__ __launch_bounds__(FTHREADS, 2) void win_fused_fwd_kernel(FusedArgs a)
 #pragma unroll
                     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) acc[dt][t] = mfma(w[2 * s + dt], xb[t][s], acc[dt][t]);
+                        for (int t = 0; t < 4; ++t) acc[dt][t] = mfma32(w[2 * s + dt], xb[t][s], acc[dt][t]);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) frag[t] = pack8(acc[0][t], acc[1][t]);
             };
@@ -278,7 +262,7 @@ __global__ __launch_bounds__(FTHREADS, 2) void win_fused_fwd_kernel(FusedArgs a)
 #pragma unroll
                         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-                            for (int t = 0; t < 4; ++t) acc[t][dt] = mfma(xb[t][s], wA[2 * s + dt], acc[t][dt]);
+                            for (int t = 0; t < 4; ++t) acc[t][dt] = mfma32(xb[t][s], wA[2 * s + dt], acc[t][dt]);
 #pragma unroll
                     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -307,8 +291,8 @@ __global__ __launch_bounds__(FTHREADS, 2) void win_fused_fwd_kernel(FusedArgs a)
                     for (int t = 0; t < 4; ++t) {
                         f32x4 vr[2];
 #pragma unroll
-                        for (int dt = 0; dt < 2; ++dt) vr[dt] = mfma(vt[t >> 1][dt], et_sel[t & 1], f32x4{0.f, 0.f, 0.f, 0.f});
-                        __builtin_amdgcn_raw_buffer_store_b128(row8(pack8(vr[0], vr[1])), vs_save, (unsigned)((16 * t + c) * (HD * 2) + d0 * 2), 0, 0);
+                        for (int dt = 0; dt < 2; ++dt) vr[dt] = mfma32(vt[t >> 1][dt], et_sel[t & 1], f32x4{0.f, 0.f, 0.f, 0.f});
+                        __builtin_amdgcn_raw_buffer_store_b128(pack_row8(vr[0], vr[1]), vs_save, (unsigned)((16 * t + c) * (HD * 2) + d0 * 2), 0, 0);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -324,7 +308,7 @@ __global__ __launch_bounds__(FTHREADS, 2) void win_fused_fwd_kernel(FusedArgs a)
 #pragma unroll
                     for (int tj = 0; tj < 4; ++tj) s4[tj] = *reinterpret_cast<const f32x4*>(bcur + (h * TOK + 16 * tq) * 256 + blane[tj]);
 #pragma unroll
-                    for (int tj = 0; tj < 4; ++tj) s4[tj] = mfma(kf[tj], qf[tq], s4[tj]);
+                    for (int tj = 0; tj < 4; ++tj) s4[tj] = mfma32(kf[tj], qf[tq], s4[tj]);
                     // softmax over the keys of the lane's query (the lane + its 3 partners 16 lanes apart)
                     float mm = s4[3][0];              // key tile 3 holds only key 48 (element 0 of group 0): the rest is -inf
 #pragma unroll
@@ -347,8 +331,8 @@ __global__ __launch_bounds__(FTHREADS, 2) void win_fused_fwd_kernel(FusedArgs a)
                     for (int s = 0; s < 2; ++s) {
                         const u32x4 pf = pack8(s4[2 * s], s4[2 * s + 1]);
 #pragma unroll
-                        for (int dt = 0; dt < 2; ++dt) o[dt] = mfma(vt[s][dt], pf, o[dt]);
-                        osum = mfma(ones, pf, osum);
+                        for (int dt = 0; dt < 2; ++dt) o[dt] = mfma32(vt[s][dt], pf, o[dt]);
+                        osum = mfma32(ones, pf, osum);
                     }
                     const float lsum = osum[0];
                     const float inv_l = 1.0f / lsum;
@@ -385,10 +369,10 @@ __global__ __launch_bounds__(FTHREADS, 2) void win_fused_fwd_kernel(FusedArgs a)
 #pragma unroll
                         for (int j = 0; j < 2; ++j)
 #pragma unroll
-                            for (int tq = 0; tq < 4; ++tq) acc[j][tq] = mfma(pw[np & 1][2 * h + j], of[h][tq], acc[j][tq]);
+                            for (int tq = 0; tq < 4; ++tq) acc[j][tq] = mfma32(pw[np & 1][2 * h + j], of[h][tq], acc[j][tq]);
 #pragma unroll
                     for (int tq = 0; tq < 4; ++tq)
-                        __builtin_amdgcn_raw_buffer_store_b128(row8(pack8(acc[0][tq], acc[1][tq])), ys,
+                        __builtin_amdgcn_raw_buffer_store_b128(pack_row8(acc[0][tq], acc[1][tq]), ys,
                                                                (unsigned)((16 * tq + c) * (FC * 2) + 64 * np + d0 * 2), 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }

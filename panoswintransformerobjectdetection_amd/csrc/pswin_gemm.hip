@@ -20,47 +20,6 @@ namespace {
 constexpr int THREADS = 256;
 using rsrc_t = __amdgpu_buffer_rsrc_t;
 
-__device__ inline f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-__device__ inline void swap16_u32(unsigned& a, unsigned& b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-    a = r[0];
-    b = r[1];
-}
-__device__ inline unsigned pack_bf16(float lo, float hi) {
-    return pack2_bf16(lo, hi);
-}
-// lane (c, g) holds quads q0 = col[4g..4g+3], q1 = col[16+4g..16+4g+3] of a 32-column group of one row -> after the
-// exchange 8 consecutive columns starting at 8 (g >> 1) + 16 (g & 1)
-__device__ inline u32x4 pack_row8(f32x4 q0, f32x4 q1) {
-    unsigned a0 = pack_bf16(q0[0], q0[1]), a1 = pack_bf16(q0[2], q0[3]);
-    unsigned b0 = pack_bf16(q1[0], q1[1]), b1 = pack_bf16(q1[2], q1[3]);
-    swap16_u32(a0, b0);
-    swap16_u32(a1, b1);
-    return u32x4{a0, a1, b0, b1};
-}
-
-// the same exchange on f32 quads (whole-vector bit casts: hipcc folds per-element casts of vector lanes)
-__device__ inline void exchange_row8(f32x4& q0, f32x4& q1) {
-    const u32x4 a = __builtin_bit_cast(u32x4, q0), b = __builtin_bit_cast(u32x4, q1);
-    unsigned a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
-    swap16_u32(a0, b0);
-    swap16_u32(a1, b1);
-    swap16_u32(a2, b2);
-    swap16_u32(a3, b3);
-    q0 = __builtin_bit_cast(f32x4, u32x4{a0, a1, a2, a3});
-    q1 = __builtin_bit_cast(f32x4, u32x4{b0, b1, b2, b3});
-}
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ inline float row16_sum(float v) {   // over the 16 lanes of a group
-    v = dpp_add<0xB1>(v);
-    v = dpp_add<0x4E>(v);
-    v = dpp_add<0x141>(v);
-    return dpp_add<0x140>(v);
-}
-
 // Epilogues.  EPI 0: y = acc + bias.  EPI 1: y = gelu(acc + bias) -- fc1 + bias + nn.GELU (HOT:50-57) in one pass, the
 // pre-activation is never stored.  EPI 2 (backward of EPI 1): the pre-activation is RECOMPUTED (K = 96: cheaper than
 // storing and re-reading 201 MB), y = aux * gelu'(acc + bias) with aux = dL/d gelu-output, and the per-column sums of
@@ -113,7 +72,7 @@ __global__ __launch_bounds__(THREADS, 2) void skinny_gemm_kernel(const void* __r
     const rsrc_t as = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(aux), 0, EPI == 2 ? (int)((size_t)M * N * 2) : 0, 0x00020000);
     constexpr int ROWS = 16 * RT;
     const int ntiles = (M + ROWS - 1) / ROWS;
-    const int d0 = 8 * (g >> 1) + 16 * (g & 1);
+    const int d0 = row8_d0(g);
     auto load_b = [&](int tile, bf16x8 (&b)[RT][KS]) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
@@ -205,7 +164,7 @@ __global__ __launch_bounds__(THREADS, 2) void skinny_gemm_kernel(const void* __r
                         v[2 * d] = __builtin_bit_cast(float, dh[d] << 16) * gg[0];
                         v[2 * d + 1] = __builtin_bit_cast(float, dh[d] & 0xffff0000u) * gg[1];
                     }
-                    const u32x4 o = {pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])};
+                    const u32x4 o = {pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])};
                     __builtin_amdgcn_raw_buffer_store_b128(o, ys, off, 0, 0);
                     // column sums over the 16 rows of the tile (lanes c of a group share the columns), then one lane per
                     // group adds them to this wave's LDS row: the kernel is HBM bound, the VALU has the slack
@@ -303,7 +262,7 @@ __global__ __launch_bounds__(M0_THREADS, 2) void mlp0_bwd_kernel(const void* __r
     const rsrc_t ds = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(dy), 0, (int)((size_t)M * K * 2), 0x00020000);
     const rsrc_t gs = __builtin_amdgcn_make_buffer_rsrc(gout, 0, (int)((size_t)M * N * 2), 0x00020000);
     const int ntiles = (M + 15) / 16;
-    const int d0 = 8 * (g >> 1) + 16 * (g & 1);
+    const int d0 = row8_d0(g);
     const int lane_off = c * 192 + (((g ^ (c >> 1)) & 3) << 4);
     bf16x8 bx[KS], bd[KS];
     auto load_b = [&](int tile) {
@@ -452,7 +411,7 @@ __global__ __launch_bounds__(M0_THREADS, 2) void mlp0_fwd_kernel(const void* __r
     const rsrc_t hs = __builtin_amdgcn_make_buffer_rsrc(hout, 0, (int)((size_t)M * N * 2), 0x00020000);
     const rsrc_t ys = __builtin_amdgcn_make_buffer_rsrc(yout, 0, (int)((size_t)M * K * 2), 0x00020000);
     const int ntiles = (M + 15) / 16;
-    const int d0 = 8 * (g >> 1) + 16 * (g & 1);
+    const int d0 = row8_d0(g);
     const int lane_off = c * 192 + (((g ^ (c >> 1)) & 3) << 4);
     // W2 fragment (output tile ot, block np): row 16 ot + c, chunk (4 np + g) ^ c = 16 (np >> 2) + ((4 (np & 3) + g) ^ c)
     const char* w2b[4];
@@ -516,7 +475,7 @@ __global__ __launch_bounds__(M0_THREADS, 2) void mlp0_fwd_kernel(const void* __r
                     q0[e] = h0[0]; q0[e + 1] = h0[1];
                     q1[e] = h1[0]; q1[e + 1] = h1[1];
                 }
-                unsigned a0 = pack_bf16(q0[0], q0[1]), a1 = pack_bf16(q0[2], q0[3]), c0 = pack_bf16(q1[0], q1[1]), c1 = pack_bf16(q1[2], q1[3]);
+                unsigned a0 = pack2_bf16(q0[0], q0[1]), a1 = pack2_bf16(q0[2], q0[3]), c0 = pack2_bf16(q1[0], q1[1]), c1 = pack2_bf16(q1[2], q1[3]);
                 const bf16x8 hf = __builtin_bit_cast(bf16x8, u32x4{a0, a1, c0, c1});
 #pragma unroll
                 for (int ot = 0; ot < OT; ++ot) ay[ot] = mfma32(w2f[ot], hf, ay[ot]);

@@ -34,41 +34,6 @@ constexpr int BN = 192, BK = 64, NT_THREADS = 256;
 #define PSWIN_NT_PROBE 0      // tools/probe/nt_probe.hip builds ablated loops (1: no loads inside the k loop, 2: loads and barriers only)
 #endif
 using rsrc_t = __amdgpu_buffer_rsrc_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-
-__device__ inline f32x4 mfma32(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ inline unsigned pk2(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2_t)); }
-// lane (c, g) holds quads q0 = col[4g..4g+3], q1 = col[16+4g..16+4g+3] of a 32-column group of one row -> after the exchange
-// 8 consecutive columns starting at 8 (g >> 1) + 16 (g & 1)
-__device__ inline u32x4 pack_row8(f32x4 q0, f32x4 q1) {
-    const unsigned a0 = pk2(q0[0], q0[1]), a1 = pk2(q0[2], q0[3]), b0 = pk2(q1[0], q1[1]), b1 = pk2(q1[2], q1[3]);
-    const auto r0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
-    const auto r1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-    return u32x4{r0[0], r1[0], r0[1], r1[1]};
-}
-
-// the same exchange on f32 quads (whole-vector bit casts: hipcc folds per-element casts of vector lanes)
-__device__ inline void exchange_row8(f32x4& q0, f32x4& q1) {
-    const u32x4 a = __builtin_bit_cast(u32x4, q0), b = __builtin_bit_cast(u32x4, q1);
-    const auto r0 = __builtin_amdgcn_permlane16_swap(a[0], b[0], false, false);
-    const auto r1 = __builtin_amdgcn_permlane16_swap(a[1], b[1], false, false);
-    const auto r2 = __builtin_amdgcn_permlane16_swap(a[2], b[2], false, false);
-    const auto r3 = __builtin_amdgcn_permlane16_swap(a[3], b[3], false, false);
-    q0 = __builtin_bit_cast(f32x4, u32x4{r0[0], r1[0], r2[0], r3[0]});
-    q1 = __builtin_bit_cast(f32x4, u32x4{r0[1], r1[1], r2[1], r3[1]});
-}
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ inline float row16_sum(float v) {   // over the 16 lanes of a group (every lane gets the sum)
-    v = dpp_add<0xB1>(v);
-    v = dpp_add<0x4E>(v);
-    v = dpp_add<0x141>(v);
-    return dpp_add<0x140>(v);
-}
 
 typedef __attribute__((address_space(3))) void lds_void;
 __device__ inline void glds16(const void* gsrc, char* lds_wave_base) {
@@ -268,7 +233,7 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(const unsigned s
                     for (int d = 0; d < 4; ++d) {
                         const gelu_f32x2 hv = gelu_f2(gelu_f32x2{__builtin_bit_cast(float, yp[d] << 16) + (d < 2 ? b0[2 * d] : b1[2 * d - 4]),
                                                                  __builtin_bit_cast(float, yp[d] & 0xffff0000u) + (d < 2 ? b0[2 * d + 1] : b1[2 * d - 3])});
-                        hp[d] = pk2(hv[0], hv[1]);
+                        hp[d] = pack2_bf16(hv[0], hv[1]);
                     }
                     __builtin_amdgcn_raw_buffer_store_b128(hp, hs, off, 0, 0);
                 }
@@ -308,7 +273,7 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(const unsigned s
                     v[2 * d] = (d < 2 ? q0[2 * d] : q1[2 * d - 4]) * gg[0];
                     v[2 * d + 1] = (d < 2 ? q0[2 * d + 1] : q1[2 * d - 3]) * gg[1];
                 }
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk2(v[0], v[1]), pk2(v[2], v[3]), pk2(v[4], v[5]), pk2(v[6], v[7])}, ys, offs[jp][i], 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])}, ys, offs[jp][i], 0, 0);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) lsum[j] += ok ? v[j] : 0.f;      // rows past M: clamped duplicates, not counted
             }

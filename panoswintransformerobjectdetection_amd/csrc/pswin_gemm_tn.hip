@@ -29,8 +29,6 @@ constexpr int MSTEP = 64, PANEL = 64 * 64 * 2;          // one [64][64] bf16 pan
 using rsrc_t = __amdgpu_buffer_rsrc_t;
 typedef __attribute__((address_space(3))) void lds_void;
 
-__device__ inline f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Round 3: the same product with a THREE-stage LDS ring.  The contraction of a weight gradient is long (256 - 2,400 rows per
 // split = 4 - 37 slabs), so unlike the forward GEMMs (3 - 12 k-steps per tile) a deep pipeline reaches steady state: the slabs of

@@ -19,41 +19,6 @@ constexpr int THREADS = 256;
 constexpr int BWD_REP = 4;
 int g_unr_fwd = 2, g_unr_bwd = 4;             // row steps per block (pswin_bias_gelu_tune)
 
-template <int DT>
-struct Vec {
-    static constexpr int VE = (DT == PSWIN_BF16) ? 8 : 4;
-};
-
-template <int DT>
-__device__ inline void load_vec(const void* base, size_t elem_off, float (&v)[Vec<DT>::VE]) {
-    if constexpr (DT == PSWIN_BF16) {
-        const u32x4 raw = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(base) + elem_off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            v[2 * e] = __builtin_bit_cast(float, raw[e] << 16);
-            v[2 * e + 1] = __builtin_bit_cast(float, raw[e] & 0xffff0000u);
-        }
-    } else {
-        const f32x4 r = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + elem_off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = r[e];
-    }
-}
-
-template <int DT>
-__device__ inline void store_vec(void* base, size_t elem_off, const float (&v)[Vec<DT>::VE]) {
-    if constexpr (DT == PSWIN_BF16) {
-        u32x4 raw;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            raw[e] = pack2_bf16(v[2 * e], v[2 * e + 1]);
-        *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(base) + elem_off) = raw;
-    } else {
-        f32x4 r = {v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(base) + elem_off) = r;
-    }
-}
-
 // grid: (row blocks, column slabs of gw groups); rps = THREADS / gw rows per step.  Streaming kernel, one short trip per
 // thread: the block owns UNR * rps CONSECUTIVE rows (a contiguous stretch of memory) and every thread issues its UNR
 // 16-byte loads (2 UNR backward) before the math.  No grid-stride loop: plain streaming kernels with a huge grid reach

@@ -275,14 +275,6 @@ __global__ void interp_rows_adjoint_kernel(const float* __restrict__ dout, const
     }
 }
 
-template <typename F>
-inline int dispatch2(int a, int b, F&& f) {
-    if (a == PSWIN_F32 && b == PSWIN_F32) return f(std::integral_constant<int, PSWIN_F32>(), std::integral_constant<int, PSWIN_F32>());
-    if (a == PSWIN_F32 && b == PSWIN_BF16) return f(std::integral_constant<int, PSWIN_F32>(), std::integral_constant<int, PSWIN_BF16>());
-    if (a == PSWIN_BF16 && b == PSWIN_F32) return f(std::integral_constant<int, PSWIN_BF16>(), std::integral_constant<int, PSWIN_F32>());
-    return f(std::integral_constant<int, PSWIN_BF16>(), std::integral_constant<int, PSWIN_BF16>());
-}
-
 inline bool rows_ok(long long rows, unsigned rpb) { return rows > 0 && (rows + rpb - 1) / rpb < (1ll << 31); }
 
 }  // namespace

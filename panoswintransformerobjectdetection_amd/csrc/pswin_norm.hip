@@ -22,10 +22,6 @@ constexpr int THREADS = 256;
 // Sum over the L lanes of a row (every lane receives it).  Steps inside a 16-lane DPP row run on the VALU
 // (v_add_f32 with a DPP modifier, ~5 cycles): __shfl_xor compiles to ds_bpermute_b32, an LDS-crossbar round trip of
 // ~100+ cycles each, and the 2 x log2(L) dependent ones per row were a quarter of a LayerNorm backward iteration.
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
 template <int L>
 __device__ inline float row_sum(float v) {
     if constexpr (L >= 2) v = dpp_add<0xB1>(v);      // quad_perm [1,0,3,2]: lane ^ 1
@@ -600,27 +596,35 @@ inline int bwd_blocks(long long rows, int L) {
     return (int)(nb < BWD_MAX_BLOCKS ? nb : BWD_MAX_BLOCKS);
 }
 
+// f(std::integral_constant<int, LL>()) for the lane counts pick_lanes() returns
+template <typename F>
+inline int with_lanes(int L, F&& f) {
+    switch (L) {
+        case 2: return f(std::integral_constant<int, 2>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 8: return f(std::integral_constant<int, 8>());
+        case 16: return f(std::integral_constant<int, 16>());
+        case 32: return f(std::integral_constant<int, 32>());
+        case 64: return f(std::integral_constant<int, 64>());
+        default: return PSWIN_ERR_ARG;
+    }
+}
+
 template <int MODE, int XDT, int YDT>
 int launch_fwd(int L, const void* x, const RowSrc& rs, const float* gamma, const float* beta, float eps, void* y,
                float* mean, float* rstd, long long rows, int C, hipStream_t st, const float* add = nullptr) {
-#define PSWIN_LN_FWD(LL)                                                                                          \
-    case LL: {                                                                                                    \
-        const int rpb = THREADS / LL;                                                                             \
-        hipLaunchKernelGGL((ln_fwd_kernel<MODE, XDT, YDT, LL, 4>), dim3((unsigned)((rows + rpb - 1) / rpb)),      \
-                           dim3(THREADS), 0, st, x, rs, gamma, beta, eps, y, mean, rstd, rows, C, add);           \
-        break;                                                                                                    \
-    }
     if (wide_row(C)) {
         hipLaunchKernelGGL((ln_fwd_kernel<MODE, XDT, YDT, 64, 8>), dim3((unsigned)((rows + 3) / 4)), dim3(THREADS), 0,
                            st, x, rs, gamma, beta, eps, y, mean, rstd, rows, C, add);
         PSWIN_LAUNCH_RET();
     }
-    switch (L) {
-        PSWIN_LN_FWD(2) PSWIN_LN_FWD(4) PSWIN_LN_FWD(8) PSWIN_LN_FWD(16) PSWIN_LN_FWD(32) PSWIN_LN_FWD(64)
-        default: return PSWIN_ERR_ARG;
-    }
-#undef PSWIN_LN_FWD
-    PSWIN_LAUNCH_RET();
+    return with_lanes(L, [&](auto ll) {
+        constexpr int LL = decltype(ll)::value;
+        const int rpb = THREADS / LL;
+        hipLaunchKernelGGL((ln_fwd_kernel<MODE, XDT, YDT, LL, 4>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(THREADS), 0,
+                           st, x, rs, gamma, beta, eps, y, mean, rstd, rows, C, add);
+        PSWIN_LAUNCH_RET();
+    });
 }
 
 template <int MODE, int DYDT, int XDT, bool RSUM>
@@ -628,26 +632,6 @@ int launch_bwd(int L, const void* dy, const int32_t* inv, const void* x, const R
                const float* rstd, const float* gamma, void* dx, const float* dres, const float* res_scale, float* part,
                long long rows, int C, int blocks, hipStream_t st, BwdExtra ex = BwdExtra{}) {
     constexpr bool CAN_EX = MODE == 0 && XDT == PSWIN_F32;
-#define PSWIN_LN_BWD(LL)                                                                                                \
-    case LL:                                                                                                            \
-        if constexpr (CAN_EX) {                                                                                         \
-            if (ex.ex) {                                                                                                \
-                if (C / 4 <= 3 * LL)                                                                                    \
-                    hipLaunchKernelGGL((ln_bwd_kernel<MODE, DYDT, XDT, LL, 3, RSUM, true>), dim3(blocks), dim3(THREADS), 0, st, dy, inv, \
-                                       x, rs, mean, rstd, gamma, dx, dres, res_scale, part, rows, C, ex);               \
-                else                                                                                                    \
-                    hipLaunchKernelGGL((ln_bwd_kernel<MODE, DYDT, XDT, LL, 4, RSUM, true>), dim3(blocks), dim3(THREADS), 0, st, dy, inv, \
-                                       x, rs, mean, rstd, gamma, dx, dres, res_scale, part, rows, C, ex);               \
-                break;                                                                                                  \
-            }                                                                                                           \
-        }                                                                                                               \
-        if (C / 4 <= 3 * LL)      /* 3 chunks per lane (C = 96, 192, 384, 768): 20 registers less, 4 waves per SIMD */      \
-            hipLaunchKernelGGL((ln_bwd_kernel<MODE, DYDT, XDT, LL, 3, RSUM>), dim3(blocks), dim3(THREADS), 0, st, dy, inv, \
-                               x, rs, mean, rstd, gamma, dx, dres, res_scale, part, rows, C, BwdExtra{});               \
-        else                                                                                                            \
-            hipLaunchKernelGGL((ln_bwd_kernel<MODE, DYDT, XDT, LL, 4, RSUM>), dim3(blocks), dim3(THREADS), 0, st, dy, inv, \
-                               x, rs, mean, rstd, gamma, dx, dres, res_scale, part, rows, C, BwdExtra{});               \
-        break;
     if (wide_row(C)) {
         if (ex.ex) return PSWIN_ERR_UNSUPPORTED;
         hipLaunchKernelGGL((ln_bwd_kernel<MODE, DYDT, XDT, 64, 8, RSUM>), dim3(blocks), dim3(THREADS), 0, st, dy, inv, x, rs,
@@ -655,20 +639,27 @@ int launch_bwd(int L, const void* dy, const int32_t* inv, const void* x, const R
         PSWIN_LAUNCH_RET();
     }
     if (ex.ex && !CAN_EX) return PSWIN_ERR_UNSUPPORTED;
-    switch (L) {
-        PSWIN_LN_BWD(2) PSWIN_LN_BWD(4) PSWIN_LN_BWD(8) PSWIN_LN_BWD(16) PSWIN_LN_BWD(32) PSWIN_LN_BWD(64)
-        default: return PSWIN_ERR_ARG;
-    }
-#undef PSWIN_LN_BWD
-    PSWIN_LAUNCH_RET();
-}
-
-template <typename F>
-inline int dispatch2(int a, int b, F&& f) {
-    if (a == PSWIN_F32 && b == PSWIN_F32) return f(std::integral_constant<int, PSWIN_F32>(), std::integral_constant<int, PSWIN_F32>());
-    if (a == PSWIN_F32 && b == PSWIN_BF16) return f(std::integral_constant<int, PSWIN_F32>(), std::integral_constant<int, PSWIN_BF16>());
-    if (a == PSWIN_BF16 && b == PSWIN_F32) return f(std::integral_constant<int, PSWIN_BF16>(), std::integral_constant<int, PSWIN_F32>());
-    return f(std::integral_constant<int, PSWIN_BF16>(), std::integral_constant<int, PSWIN_BF16>());
+    return with_lanes(L, [&](auto ll) {
+        constexpr int LL = decltype(ll)::value;
+        if constexpr (CAN_EX) {
+            if (ex.ex) {
+                if (C / 4 <= 3 * LL)
+                    hipLaunchKernelGGL((ln_bwd_kernel<MODE, DYDT, XDT, LL, 3, RSUM, true>), dim3(blocks), dim3(THREADS), 0, st, dy, inv,
+                                       x, rs, mean, rstd, gamma, dx, dres, res_scale, part, rows, C, ex);
+                else
+                    hipLaunchKernelGGL((ln_bwd_kernel<MODE, DYDT, XDT, LL, 4, RSUM, true>), dim3(blocks), dim3(THREADS), 0, st, dy, inv,
+                                       x, rs, mean, rstd, gamma, dx, dres, res_scale, part, rows, C, ex);
+                PSWIN_LAUNCH_RET();
+            }
+        }
+        if (C / 4 <= 3 * LL)      // 3 chunks per lane (C = 96, 192, 384, 768): 20 registers less, 4 waves per SIMD
+            hipLaunchKernelGGL((ln_bwd_kernel<MODE, DYDT, XDT, LL, 3, RSUM>), dim3(blocks), dim3(THREADS), 0, st, dy, inv,
+                               x, rs, mean, rstd, gamma, dx, dres, res_scale, part, rows, C, BwdExtra{});
+        else
+            hipLaunchKernelGGL((ln_bwd_kernel<MODE, DYDT, XDT, LL, 4, RSUM>), dim3(blocks), dim3(THREADS), 0, st, dy, inv,
+                               x, rs, mean, rstd, gamma, dx, dres, res_scale, part, rows, C, BwdExtra{});
+        PSWIN_LAUNCH_RET();
+    });
 }
 
 }  // namespace
@@ -722,21 +713,14 @@ extern "C" int pswin_scatter_add_ln_fwd_map(const void* win, int win_dtype, cons
     const int L = pick_lanes(C);
     hipStream_t st = (hipStream_t)stream;
     return dispatch2(win_dtype, y_dtype, [&](auto wd, auto yd) {
-#define PSWIN_LN_ADD(LL)                                                                                                   \
-    case LL: {                                                                                                             \
-        const int rpb = THREADS / LL;                                                                                      \
-        hipLaunchKernelGGL((ln_add_fwd_kernel<decltype(wd)::value, decltype(yd)::value, LL, 4>),                            \
-                           dim3((unsigned)((groups + rpb - 1) / rpb)), dim3(THREADS), 0, st, win, inv, resid, scale, bias, x1, \
-                           gamma, beta, eps, y, mean, rstd, rows, S, n_slots, C, om);                                      \
-        break;                                                                                                             \
-    }
-        switch (L) {
-            PSWIN_LN_ADD(2) PSWIN_LN_ADD(4) PSWIN_LN_ADD(8) PSWIN_LN_ADD(16) PSWIN_LN_ADD(32) PSWIN_LN_ADD(64)
-            default: return (int)PSWIN_ERR_ARG;
-        }
-#undef PSWIN_LN_ADD
-        hipError_t e__ = hipGetLastError();
-        return e__ == hipSuccess ? (int)PSWIN_OK : (int)e__;
+        return with_lanes(L, [&](auto ll) {
+            constexpr int LL = decltype(ll)::value;
+            const int rpb = THREADS / LL;
+            hipLaunchKernelGGL((ln_add_fwd_kernel<decltype(wd)::value, decltype(yd)::value, LL, 4>),
+                               dim3((unsigned)((groups + rpb - 1) / rpb)), dim3(THREADS), 0, st, win, inv, resid, scale, bias, x1,
+                               gamma, beta, eps, y, mean, rstd, rows, S, n_slots, C, om);
+            PSWIN_LAUNCH_RET();
+        });
     });
 }
 
@@ -856,17 +840,11 @@ extern "C" int pswin_scatter_add_ln_nchw_fwd(const void* win_bf16, const float* 
     const long long rows = (long long)B * S;
     const unsigned grid = (unsigned)(rows / rpb);
     const size_t lds = (size_t)C * (rpb + 1) * sizeof(float);
-#define PSWIN_LN_NCHW_F(LL)                                                                                               \
-    case LL:                                                                                                              \
-        hipLaunchKernelGGL((ln_nchw_fwd_kernel<LL, 4>), dim3(grid), dim3(THREADS), lds, (hipStream_t)stream, x, gamma, beta, \
-                           eps, y, mean, rstd, S, C, reinterpret_cast<const unsigned short*>(win), scale, bias, x1);       \
-        break;
-    switch (L) {
-        PSWIN_LN_NCHW_F(2) PSWIN_LN_NCHW_F(4) PSWIN_LN_NCHW_F(8) PSWIN_LN_NCHW_F(16) PSWIN_LN_NCHW_F(32) PSWIN_LN_NCHW_F(64)
-        default: return PSWIN_ERR_ARG;
-    }
-#undef PSWIN_LN_NCHW_F
-    PSWIN_LAUNCH_RET();
+    return with_lanes(L, [&](auto ll) {
+        hipLaunchKernelGGL((ln_nchw_fwd_kernel<decltype(ll)::value, 4>), dim3(grid), dim3(THREADS), lds, (hipStream_t)stream, x, gamma,
+                           beta, eps, y, mean, rstd, S, C, reinterpret_cast<const unsigned short*>(win), scale, bias, x1);
+        PSWIN_LAUNCH_RET();
+    });
 }
 
 extern "C" int pswin_ln_nchw_fwd(const float* x, const float* gamma, const float* beta, float eps, float* y, float* mean,
@@ -884,16 +862,12 @@ extern "C" int pswin_ln_nchw_bwd_ex(const float* dy, const float* x, const float
     const long long rows = (long long)B * S;
     const int blocks = bwd_blocks(rows, L);
     const size_t lds = (size_t)rpb * (C + 4) * sizeof(float);
-#define PSWIN_LN_NCHW_B(LL)                                                                                              \
-    case LL:                                                                                                             \
-        hipLaunchKernelGGL((ln_nchw_bwd_kernel<LL, 4>), dim3(blocks), dim3(THREADS), lds, (hipStream_t)stream, dy, x, mean, \
-                           rstd, gamma, dres, dx, workspace, rows, S, C, ex_bf16, ex_scale);                             \
-        break;
-    switch (L) {
-        PSWIN_LN_NCHW_B(2) PSWIN_LN_NCHW_B(4) PSWIN_LN_NCHW_B(8) PSWIN_LN_NCHW_B(16) PSWIN_LN_NCHW_B(32) PSWIN_LN_NCHW_B(64)
-        default: return PSWIN_ERR_ARG;
-    }
-#undef PSWIN_LN_NCHW_B
+    const int rc = with_lanes(L, [&](auto ll) {
+        hipLaunchKernelGGL((ln_nchw_bwd_kernel<decltype(ll)::value, 4>), dim3(blocks), dim3(THREADS), lds, (hipStream_t)stream, dy, x,
+                           mean, rstd, gamma, dres, dx, workspace, rows, S, C, ex_bf16, ex_scale);
+        return PSWIN_OK;
+    });
+    if (rc) return rc;
     if (dgamma) launch_colsum_seg(workspace, blocks, C, 2, dgamma, dbeta, nullptr, (hipStream_t)stream);
     PSWIN_LAUNCH_RET();
 }

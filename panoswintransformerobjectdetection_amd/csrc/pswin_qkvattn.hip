@@ -46,17 +46,6 @@ struct QkvAttnArgs {
     int group;              // bias windows a workgroup has in LDS at a time (round 4): 1, or 8 / reps' for small batches
 };
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-__device__ inline unsigned pk(float lo, float hi) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2)); }
-__device__ inline u32x4 pack8(f32x4 lo, f32x4 hi) { return u32x4{pk(lo[0], lo[1]), pk(lo[2], lo[3]), pk(hi[0], hi[1]), pk(hi[2], hi[3])}; }
-__device__ inline u32x4 row8(u32x4 f) {
-    const auto r0 = __builtin_amdgcn_permlane16_swap(f[0], f[2], false, false);
-    const auto r1 = __builtin_amdgcn_permlane16_swap(f[1], f[3], false, false);
-    return u32x4{r0[0], r1[0], r0[1], r1[1]};
-}
-__device__ inline f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 __device__ inline int bias_off1(int i, int q) { return (i * 16 + ((q + 2 * i) & 15)) * 16; }   // bytes: [query][key quad], quads rotated by 2 * query
 
 #ifdef PSWIN_QA_PROBE
@@ -133,7 +122,7 @@ __global__ __launch_bounds__(QTHREADS, 2) void qkv_attn_fwd_kernel(QkvAttnArgs a
     }
     const float inv_scale = 1.0f / a.scale;
     const float sl2e = a.scale * LOG2E;
-    const int d0 = 8 * (g >> 1) + 16 * (g & 1);       // first of this lane's 8 contiguous columns after row8()
+    const int d0 = row8_d0(g);   // first of this lane's 8 contiguous columns after row8()
     // weight fragment (rows R + c, channels 32 s + 8 g ..): R * PITCH + ((4 s + g) ^ c) * 16 with R a multiple of 16.  The XOR only
     // touches the low four chunk bits, so (4 s + g) ^ c = 16 (s >> 2) + ((4 (s & 3) + g) ^ c): four lane bases, the rest immediates
     // (a base per step, as the expression reads, is twelve loop-invariant registers the unrolled loop then spills).
@@ -196,13 +185,10 @@ __global__ __launch_bounds__(QTHREADS, 2) void qkv_attn_fwd_kernel(QkvAttnArgs a
     // in flight and runs on across items: the first steps of a wave's NEXT window are requested during the last steps of the
     // current one, so the score / softmax / P.V chain of an item hides the round trip of the next.  Slot of step s of an item that
     // starts at ring phase PH: (PH + s) % XD; the next item starts at (PH + KS) % XD = PH for both geometries.
-#ifndef PSWIN_QA_XD_INFER
-#define PSWIN_QA_XD_INFER 4
-#endif
     // slots: four (one pair in flight behind the pair in use) at C = 384; C = 192 (six steps) takes six, or three single steps in the
     // training variant, which has no registers for six.  Same-box A/B of four against six slots at C = 384: equal within 1 %
     // (the k loop is not waiting on latency any more; MFMA issue, the L1 / address path and LDS reads each sit at 50-100 %).
-    constexpr int XD = SAVE ? ((KS % 4 == 0) ? 4 : 3) : (KS % PSWIN_QA_XD_INFER == 0) ? PSWIN_QA_XD_INFER : 6;
+    constexpr int XD = (KS % 4 == 0) ? 4 : SAVE ? 3 : 6;
     constexpr bool PAIRS = XD % 2 == 0;
     u32x4 xr[6][4];
     const char* xbase = reinterpret_cast<const char*>(a.x);
@@ -274,9 +260,9 @@ __global__ __launch_bounds__(QTHREADS, 2) void qkv_attn_fwd_kernel(QkvAttnArgs a
                     const int p_ = f >> 1, dt = f & 1;
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
-                        if (p_ == 0) aq[dt][t] = mfma(w[f], xf[t], aq[dt][t]);            // Q^T [d][token]
-                        else if (p_ == 1) ak[dt][t] = mfma(w[f], xf[t], ak[dt][t]);       // K^T
-                        else av[t][dt] = mfma(xf[t], w[f], av[t][dt]);                    // V [token][d]
+                        if (p_ == 0) aq[dt][t] = mfma32(w[f], xf[t], aq[dt][t]);            // Q^T [d][token]
+                        else if (p_ == 1) ak[dt][t] = mfma32(w[f], xf[t], ak[dt][t]);       // K^T
+                        else av[t][dt] = mfma32(xf[t], w[f], av[t][dt]);                    // V [token][d]
                     }
                     if (s + 1 < KS)
                         w[f] = *reinterpret_cast<const u32x4*>(w_l[(s + 1) & 3] + (32 * p_ + 16 * dt) * PITCH + ((s + 1) >> 2) * 256);
@@ -328,8 +314,8 @@ __global__ __launch_bounds__(QTHREADS, 2) void qkv_attn_fwd_kernel(QkvAttnArgs a
             for (int t = 0; t < 4; ++t) {
                 f32x4 vr[2];
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) vr[dt] = mfma(vt[t >> 1][dt], et[t & 1], f32x4{0.f, 0.f, 0.f, 0.f});
-                __builtin_amdgcn_raw_buffer_store_b128(row8(pack8(vr[0], vr[1])), vs, ro + 16 * t * (HD * 2), 0, 0);
+                for (int dt = 0; dt < 2; ++dt) vr[dt] = mfma32(vt[t >> 1][dt], et[t & 1], f32x4{0.f, 0.f, 0.f, 0.f});
+                __builtin_amdgcn_raw_buffer_store_b128(pack_row8(vr[0], vr[1]), vs, ro + 16 * t * (HD * 2), 0, 0);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -344,7 +330,7 @@ __global__ __launch_bounds__(QTHREADS, 2) void qkv_attn_fwd_kernel(QkvAttnArgs a
 #pragma unroll
             for (int tj = 0; tj < 4; ++tj) s4[tj] = *reinterpret_cast<const f32x4*>(bcur + 16 * tq * 256 + blane[tj]);
 #pragma unroll
-            for (int tj = 0; tj < 4; ++tj) s4[tj] = mfma(kf[tj], qf[tq], s4[tj]);
+            for (int tj = 0; tj < 4; ++tj) s4[tj] = mfma32(kf[tj], qf[tq], s4[tj]);
             float mm = s4[3][0];                  // key tile 3 holds only key 48 (element 0 of group 0): the rest is -inf
 #pragma unroll
             for (int tj = 0; tj < 3; ++tj)
@@ -362,13 +348,13 @@ __global__ __launch_bounds__(QTHREADS, 2) void qkv_attn_fwd_kernel(QkvAttnArgs a
             for (int s = 0; s < 2; ++s) {
                 const u32x4 pf = pack8(s4[2 * s], s4[2 * s + 1]);
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) o[dt] = mfma(vt[s][dt], pf, o[dt]);
-                osum = mfma(ones, pf, osum);
+                for (int dt = 0; dt < 2; ++dt) o[dt] = mfma32(vt[s][dt], pf, o[dt]);
+                osum = mfma32(ones, pf, osum);
             }
             const float lsum = osum[0];
             const float inv_l = 1.0f / lsum;
             const int i = 16 * tq + c;
-            __builtin_amdgcn_raw_buffer_store_b128(row8(pack8(o[0] * inv_l, o[1] * inv_l)), as, (unsigned)(c * (C * 2) + d0 * 2), 16 * tq * (C * 2), 0);
+            __builtin_amdgcn_raw_buffer_store_b128(pack_row8(o[0] * inv_l, o[1] * inv_l), as, (unsigned)(c * (C * 2) + d0 * 2), 16 * tq * (C * 2), 0);
             if constexpr (SAVE) {
                 if (g == 0) a.lse[(win * heads + hh) * PADT + i] = (i < TOK) ? __builtin_fmaf(mm, a.scale, logf(lsum)) : INFINITY;
             }

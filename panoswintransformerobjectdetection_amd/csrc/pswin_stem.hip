@@ -35,7 +35,6 @@ typedef unsigned long long u64;
 using rsrc_t = __amdgpu_buffer_rsrc_t;
 
 __device__ inline f32x4 mfma16(s16x4 a, s16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0); }
-__device__ inline f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 // LDS images with power-of-two rows, 16-byte chunks XOR-swizzled by the row so that both the row-wise 16-byte accesses
 // of 8 consecutive rows and the transposed 8-byte reads (8 rows x 32 bytes per half wave) are bank-conflict free
@@ -52,65 +51,8 @@ __device__ inline bf16x8 tr_pair(const char* lo, const char* hi) {
     return __builtin_bit_cast(bf16x8, both);
 }
 
-template <int CTRL>
-__device__ inline float dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ inline float row16_sum(float v) {   // over the 16 lanes of a group
-    v = dpp_add<0xB1>(v);
-    v = dpp_add<0x4E>(v);
-    v = dpp_add<0x141>(v);
-    return dpp_add<0x140>(v);
-}
-// v_permlane16_swap: exchanges the odd 16-lane rows of a with the even rows of b.  The builtin (not inline asm) so that
-// the compiler's hazard recognizer sees the instruction: its operands often come straight from MFMA accumulators, and
-// the MFMA-write -> VALU-read wait states are software managed (an asm version with a fixed s_nop read stale values).
-__device__ inline void swap16_u32(unsigned& a, unsigned& b) {
-    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-    a = r[0];
-    b = r[1];
-}
-
-// One v_cvt_pk_bf16_f32 per pair (pack2_bf16).  Round 2 kept the two-conversion form here because the short form produced non-finite
-// weight gradients; round 3 found why (it was never the conversion): the store of stem_conv3_bwd_kernel<true> below -- see the comment
-// there.  PSWIN_STEM_PACK2=0 builds the old form (A/B).
-#ifndef PSWIN_STEM_PACK2
-#define PSWIN_STEM_PACK2 1
-#endif
-__device__ inline unsigned pack_bf16(float lo, float hi) {
-#if PSWIN_STEM_PACK2
-    return pack2_bf16(lo, hi);
-#else
-    return (unsigned)f32_to_bf16_bits(lo) | ((unsigned)f32_to_bf16_bits(hi) << 16);
-#endif
-}
 __device__ inline float bf_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ inline float bf_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-
-// A lane (c, g) holds for one pixel / token the accumulator quads q0 = ch[4g..4g+3] and q1 = ch[16+4g..16+4g+3] of a
-// 32-channel group; after exchanging q1 of the even groups with q0 of the odd ones every lane owns 8 consecutive
-// channels starting at d0 = 8 (g >> 1) + 16 (g & 1): returned packed as 4 dwords of bf16 pairs.
-__device__ inline u32x4 pack_row8(int g, f32x4 q0, f32x4 q1) {
-    unsigned a0 = pack_bf16(q0[0], q0[1]), a1 = pack_bf16(q0[2], q0[3]);
-    unsigned b0 = pack_bf16(q1[0], q1[1]), b1 = pack_bf16(q1[2], q1[3]);
-    swap16_u32(a0, b0);
-    swap16_u32(a1, b1);
-    (void)g;
-    return u32x4{a0, a1, b0, b1};
-}
-// the same exchange on f32 quads (8 consecutive channels as two quads).  Whole-vector bit casts only: hipcc (ROCm 7.2)
-// folds __builtin_bit_cast(T, vec[e]) inside an unrolled loop to element 0.
-__device__ inline void exchange_row8(f32x4& q0, f32x4& q1) {
-    const u32x4 a = __builtin_bit_cast(u32x4, q0), b = __builtin_bit_cast(u32x4, q1);
-    unsigned a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
-    swap16_u32(a0, b0);
-    swap16_u32(a1, b1);
-    swap16_u32(a2, b2);
-    swap16_u32(a3, b3);
-    q0 = __builtin_bit_cast(f32x4, u32x4{a0, a1, a2, a3});
-    q1 = __builtin_bit_cast(f32x4, u32x4{b0, b1, b2, b3});
-}
-__device__ inline int row8_d0(int g) { return 8 * (g >> 1) + 16 * (g & 1); }
 
 // ---------------------------------------------------------------------------------------------
 // input repack: [B,3,H,W] f32 -> [B,H,W,4] bf16, channel 3 = 1
@@ -120,8 +62,8 @@ __global__ void stem_pack_kernel(const float* __restrict__ x, long long npix_per
     if (i >= total) return;
     const long long b = i / npix_per_img, p = i - b * npix_per_img;
     const float* src = x + b * 3 * npix_per_img + p;
-    const unsigned lo = pack_bf16(src[0], src[npix_per_img]);
-    const unsigned hi = pack_bf16(src[2 * npix_per_img], 1.0f);
+    const unsigned lo = pack2_bf16(src[0], src[npix_per_img]);
+    const unsigned hi = pack2_bf16(src[2 * npix_per_img], 1.0f);
     x4[i] = (u64)lo | ((u64)hi << 32);
 }
 
@@ -130,9 +72,7 @@ __global__ void stem_pack_kernel(const float* __restrict__ x, long long npix_per
 // ---------------------------------------------------------------------------------------------
 constexpr int W3S_BYTES = C3 * 128;          // one tap slice [96 out][64 in]
 constexpr int TOK_WG = TNW * 16;              // 128 tokens per workgroup and token tile
-#ifndef PSWIN_STEM_CONV3_TT
-#define PSWIN_STEM_CONV3_TT 4                 // token tiles per wave in the conv3 forward kernel (A/B builds: 1, 2)
-#endif
+constexpr int CONV3_TT = 4;                   // token tiles per wave in the conv3 forward kernel
 
 struct TokGeo {
     long long pix;       // pixel index of the token's top-left pixel in [B][H][W]
@@ -151,7 +91,7 @@ __device__ inline bf16x8 bn_relu8(u32x4 raw, const float (&sc)[8], const float (
     for (int d = 0; d < 4; ++d) {
         const float lo = fmaxf(__builtin_fmaf(bf_lo(raw[d]), sc[2 * d], sh[2 * d]), 0.f);
         const float hi = fmaxf(__builtin_fmaf(bf_hi(raw[d]), sc[2 * d + 1], sh[2 * d + 1]), 0.f);
-        o[d] = pack_bf16(lo, hi);
+        o[d] = pack2_bf16(lo, hi);
     }
     return __builtin_bit_cast(bf16x8, o);
 }
@@ -268,7 +208,7 @@ __global__ __launch_bounds__(TWG) void stem_conv3_fwd_kernel(const void* __restr
         char* dst = reinterpret_cast<char*>(tok_out) + tok[t] * (C3 * 2) + row8_d0(g) * 2;
 #pragma unroll
         for (int pr = 0; pr < 3; ++pr) {
-            const u32x4 v = pack_row8(g, acc[t][2 * pr], acc[t][2 * pr + 1]);
+            const u32x4 v = pack_row8(acc[t][2 * pr], acc[t][2 * pr + 1]);
             if (valid[t]) *reinterpret_cast<u32x4*>(dst + pr * 64) = v;
         }
     }
@@ -438,7 +378,7 @@ __global__ __launch_bounds__(TWG, 2) void stem_conv3_bwd_kernel(const void* __re
                         }
                     }
                     if constexpr (APPLY) {
-                        const u32x4 o = {pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])};
+                        const u32x4 o = {pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])};
                         // The tap offset rides in the VECTOR offset, not in the scalar one.  hipcc's hazard recognizer pads a 128-bit buffer
                         // store against the next VALU write of its data registers only when the store has NO scalar-register offset (the rule
                         // of the older GCN parts); with `soff` in an SGPR it pads nothing, and the next pixel's arithmetic, which reuses the
@@ -617,7 +557,7 @@ __global__ __launch_bounds__(TWG, 4) void stem_conv3_wgrad_kernel(const void* __
             for (int d = 0; d < 4; ++d) {
                 const float lo = fmaxf(__builtin_fmaf(bf_lo(raw[d]), scl[nt], shl[nt]), 0.f);
                 const float hi = fmaxf(__builtin_fmaf(bf_hi(raw[d]), scl[nt], shl[nt]), 0.f);
-                o[d] = pack_bf16(lo, hi);
+                o[d] = pack2_bf16(lo, hi);
             }
             const bf16x8 b = __builtin_bit_cast(bf16x8, o);
 #pragma unroll
@@ -837,9 +777,8 @@ int pswin_stem_conv3_fwd(const void* y2, const float* scale2, const float* shift
                          int B, int H, int W, void* tokens, void* stream) {
     PSWIN_CHECK_ARG(y2 && scale2 && shift2 && w3p && bias3 && tokens && B > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0);
     const long long M = (long long)B * (H / 4) * (W / 4);
-    constexpr int TT = PSWIN_STEM_CONV3_TT;
-    const unsigned grid = (unsigned)((M + TOK_WG * TT - 1) / (TOK_WG * TT));
-    hipLaunchKernelGGL(stem_conv3_fwd_kernel<TT>, dim3(grid), dim3(TWG), 0, (hipStream_t)stream, y2, scale2, shift2, w3p, bias3, H,
+    const unsigned grid = (unsigned)((M + TOK_WG * CONV3_TT - 1) / (TOK_WG * CONV3_TT));
+    hipLaunchKernelGGL(stem_conv3_fwd_kernel<CONV3_TT>, dim3(grid), dim3(TWG), 0, (hipStream_t)stream, y2, scale2, shift2, w3p, bias3, H,
                        W, M, (long long)B * H * W * 128, tokens);
     PSWIN_LAUNCH_RET();
 }

@@ -175,7 +175,7 @@ __device__ inline void build_a1(const char* xs, const W1Frags& w, const float (&
                 const float z = fmaxf(__builtin_fmaf(acc[nt][e], sc[nt][e], sh[nt][e]), 0.f);
                 v[e] = in ? z : 0.f;
             }
-            u32x2 pk = {pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
+            u32x2 pk = {pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])};
             const int Pl = ACP == AC ? P : (P / AC) * ACP + (P - (P / AC) * AC);       // pixel index in the image's row pitch
             *reinterpret_cast<u32x2*>(a1s + off64(Pl, 2 * nt + (g >> 1)) + (g & 1) * 8) = pk;
         }
@@ -397,8 +397,8 @@ __global__ __launch_bounds__(WG, 2) void stem_conv2_fwd_kernel(const u64* __rest
                     }
             }
             const unsigned poff = in ? (unsigned)(gy * W + gx) * 128u + (unsigned)row8_d0(g) * 2u : 0xFFFFFF00u;
-            __builtin_amdgcn_raw_buffer_store_b128(pack_row8(g, acc[pt][0], acc[pt][1]), ys, poff, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(pack_row8(g, acc[pt][2], acc[pt][3]), ys, poff + 64u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(pack_row8(acc[pt][0], acc[pt][1]), ys, poff, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(pack_row8(acc[pt][2], acc[pt][3]), ys, poff + 64u, 0, 0);
         }
     }
     if (partial) {
@@ -627,7 +627,7 @@ __global__ __launch_bounds__(WG, 2) void stem_conv2_bwd_kernel(const u64* __rest
                     sgy[nt][e] = __builtin_fmaf(gg, yh, sgy[nt][e]);
                     v[e] = gg;
                 }
-                gp[pt][nt] = u32x2{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
+                gp[pt][nt] = u32x2{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])};
             }
         }
         __syncthreads();                               // every wave is done with the dy2 tile
