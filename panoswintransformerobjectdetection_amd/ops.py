@@ -4,6 +4,7 @@ Every function here launches hand-written gfx950 kernels from libpswin_hip.so on
 There is no PyTorch/CPU fallback: a CPU tensor or a missing library raises ``PswinError``.
 Reference file:line citations use HOT = mmdet/models/backbones/simple_panoswin_transformer.py.
 """
+import ctypes
 import math
 import os
 
@@ -11,7 +12,10 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from . import grad_queue
 from ._lib import BF16, F32, MODE_PANO, MODE_PLANAR, WPAD, WTOK, PswinError, call, dtype_code, ptr
+# the end-of-pass gradient queue: every "sum these partial rows" of the backward pass goes through sum_rows
+from .grad_queue import deferred_reductions_available, flush_if_pending, flush_reductions, grad_slot, set_deferred_reductions, sum_rows  # noqa: F401
 
 _CACHE = {}
 # Feature switches.  Every one of them selects between two HIP paths (a fused kernel or the chain of kernels it replaces), never a CPU
@@ -33,6 +37,8 @@ GEMM_NT = _on("gemm_nt")
 FUSED_GELU_BWD = _on("fused_gelu_bwd")
 # fc1 with the bias + GELU in its epilogue (pswin_gemm_nt_gelu_fwd) and fc2 as one autograd node; off: GEMM, then a streaming bias + GELU pass
 FUSED_MLP = _on("fused_mlp")
+# off: the dScore-tile sums of an attention module run inside its backward instead of in one launch at the end of the pass
+DEFER_TABLE_PARTIALS = _on("defer_table_partials")
 
 
 def _dev_key(device):
@@ -42,221 +48,6 @@ def _dev_key(device):
 
 def clear_caches():
     _CACHE.clear()
-
-
-# ------------------------------------------------------------------------------------------------
-# parameter-gradient reductions: every "sum these partial rows" of the backward pass goes through sum_rows
-# ------------------------------------------------------------------------------------------------
-class _ReduceQueue:
-    enabled = False
-    # autograd graph task id -> jobs queued by that backward pass.  Keyed by task because passes nest (the backward of a
-    # torch.utils.checkpoint segment is a pass of its own inside the outer one); each pass flushes its own jobs.
-    #   "jobs": (src tensor, byte offset, dtype code, rows, cols, ld, dst tensor)
-    #   "wgrad_jobs": weight gradients held back for the grouped launch (dy, x, partial, bias partial or None, M, N, K, splits, zero_lo, zero_hi)
-    #   "table_jobs": attention table gradients waiting for their binning launch (after the reductions)
-    #   "owners": data_ptr of every parameter that already has a postponed gradient in this pass
-    tasks = {}
-    slots = {}           # graph task id -> flat-gradient slots already handed out in that pass (grad_slot)
-
-    @staticmethod
-    def trim(d):         # leftovers of passes that raised: keep the table small (task ids grow monotonically)
-        while len(d) > 8:
-            del d[min(d)]
-
-
-def _graph_task_id():
-    """id of the running backward pass (-1 outside one).  A private torch entry point (present in torch 2.1 .. 2.10): without it
-    nothing is postponed and no gradient slot is handed out -- every reduction launches where it is issued."""
-    f = getattr(torch._C, "_current_graph_task_id", None)
-    return f() if f is not None else -1
-
-
-def deferred_reductions_available():
-    """The two private torch entry points the end-of-pass grouping relies on (the id of the running backward pass and the
-    autograd engine's end-of-pass callback) exist in this torch build."""
-    eng = getattr(torch.autograd.Variable, "_execution_engine", None)
-    return hasattr(torch._C, "_current_graph_task_id") and eng is not None and hasattr(eng, "queue_callback")
-
-
-def set_deferred_reductions(on):
-    """on=True: reductions whose result is a PARAMETER gradient (split-K partials of dW, bias-gradient partial rows,
-    LayerNorm dgamma / dbeta rows) are queued while autograd runs and issued as one grouped launch when the backward pass
-    ends (an autograd engine callback), instead of ~120 launches of 5-8 us each.  A postponed gradient tensor is filled
-    only once backward() returns, so a reduction is postponed only when nothing can read its result earlier: the
-    call site names the parameter(s) the result belongs to (``owners``), and the launch stays immediate when an owner
-    already holds a ``.grad`` (autograd would accumulate into it at once), carries a tensor / post-accumulate hook
-    (dp.GradReducer(pack=False) launches its all-reduce from one), or already received a postponed gradient in the same
-    pass (a module applied twice: autograd adds the two as soon as the second arrives; the queue is flushed first).
-    NOT covered: hooks registered on a parameter's AccumulateGrad NODE (torch DistributedDataParallel's reducer,
-    ``grad_fn.register_hook`` consumers) are invisible from Python and would read unfilled gradients -- use dp.GradReducer (which
-    this mode is built for) or leave deferral off under DDP.  Returns the previous setting."""
-    if on and not deferred_reductions_available():
-        raise PswinError("set_deferred_reductions(True) needs torch._C._current_graph_task_id and the autograd engine's queue_callback "
-                         f"(private entry points, present in torch 2.1 - 2.10; this is torch {torch.__version__})")
-    prev, _ReduceQueue.enabled = _ReduceQueue.enabled, bool(on)
-    return prev
-
-
-def _launch_reductions(jobs):
-    import ctypes
-    by_dev = {}
-    for j in jobs:
-        by_dev.setdefault(j[0].device, []).append(j)
-    for lst in by_dev.values():
-        arr = (_lib.ReduceJob * len(lst))()
-        for a, (src, off, dt, rows, cols, ld, dst) in zip(arr, lst):
-            a.src, a.dst, a.dtype, a.rows, a.cols, a.ld = src.data_ptr() + off, dst.data_ptr(), dt, rows, cols, ld
-        call("pswin_reduce_jobs", lst[0][0], ctypes.cast(arr, ctypes.c_void_p), len(lst))
-
-
-# off: the dScore-tile sums of an attention module run inside its backward instead of in one launch at the end of the pass
-DEFER_TABLE_PARTIALS = _on("defer_table_partials")
-
-
-def _launch_table_grads(jobs, stages=3):
-    import ctypes
-    by_dev = {}
-    for j in jobs:
-        by_dev.setdefault(j[0].device, []).append(j)
-    for lst in by_dev.values():
-        arr = (_lib.TableGradJob * len(lst))()
-        for a, (gsum, dist_t, dalpha, dbeta, ws, n_tiles, nb, n_dist, heads) in zip(arr, lst):
-            a.dscore_sum, a.dist_tiles_t = gsum.data_ptr(), (None if dist_t is None else dist_t.data_ptr())
-            a.dalpha, a.dbeta, a.workspace = (None if dalpha is None else dalpha.data_ptr()), dbeta.data_ptr(), ws.data_ptr()
-            a.n_tiles, a.n_bias_windows, a.n_dist, a.heads = n_tiles, nb, n_dist, heads
-        call("pswin_attn_table_grads_batch", lst[0][0], ctypes.cast(arr, ctypes.c_void_p), len(lst), stages)
-
-
-def _launch_wgrads(jobs):
-    """The queued weight gradients as ONE pswin_gemm_tn_ring_jobs call per device (one kernel launch per tile geometry): longest row
-    ranges first, so that the tail of the launch is made of the short ones."""
-    import ctypes
-    by_dev = {}
-    for j in jobs:
-        by_dev.setdefault(j[0].device, []).append(j)
-    for lst in by_dev.values():
-        lst = sorted(lst, key=lambda j: -(j[4] // j[7]))
-        arr = (_lib.TnJob * len(lst))()
-        nbytes = flops = pbytes = 0
-        for a, (dy, x, part, dbp, M, N, K, splits, zlo, zhi) in zip(arr, lst):
-            a.dy, a.x, a.partial, a.dbias_partial = dy.data_ptr(), x.data_ptr(), part.data_ptr(), (None if dbp is None else dbp.data_ptr())
-            a.M, a.N, a.K, a.splits, a.partial_dtype, a.zero_lo, a.zero_hi = M, N, K, splits, dtype_code(part), zlo, zhi
-            nbytes += 2 * (M * K + M * N) + 4 * N * K
-            flops += 2 * M * K * N
-            pbytes += part.element_size() * splits * N * K if splits > 1 else 0
-        call("pswin_gemm_tn_ring_jobs", lst[0][0], ctypes.cast(arr, ctypes.c_void_p), len(lst), algo_bytes=nbytes, algo_flops=flops,
-             timed_as="pswin_gemm_tn_ring", partial_bytes=pbytes)
-
-
-def _launch_queue(q):
-    jobs, tjobs, wjobs = q["jobs"], q["table_jobs"], q["wgrad_jobs"]
-    q["jobs"], q["table_jobs"], q["wgrad_jobs"] = [], [], []
-    if wjobs:
-        _launch_wgrads(wjobs)                           # the reductions below sum their partial slabs
-    if tjobs and DEFER_TABLE_PARTIALS:
-        _launch_table_grads(tjobs, 1)                   # partial-row sums of every attention module's dScore tiles, one launch
-    if jobs:
-        _launch_reductions(jobs)
-    if tjobs:
-        _launch_table_grads(tjobs, 4)                   # per-bin sums from the partial-row sums the reductions just wrote
-
-
-def flush_reductions(task=None):
-    """Issue the reductions queued by one backward pass (runs by itself when that pass ends); task=None: all of them."""
-    keys = list(_ReduceQueue.tasks) if task is None else [task]
-    for k in keys:
-        q = _ReduceQueue.tasks.pop(k, None)
-        if q is not None:
-            _launch_queue(q)
-
-
-def _has_hooks(p):
-    return bool(getattr(p, "_post_accumulate_grad_hooks", None)) or bool(getattr(p, "_backward_hooks", None))
-
-
-def _deferring(owners=()):
-    """The job queue of the running backward pass if the reduction that produces the gradients of `owners` (parameters)
-    may be postponed to the end of that pass (see set_deferred_reductions; the end-of-pass callback is armed on first
-    use), else None = launch now.  Without owners the destination is unknown and nothing is postponed."""
-    task = _graph_task_id() if _ReduceQueue.enabled else -1
-    owners = [o for o in owners if o is not None]
-    if task == -1 or not owners:
-        return None
-    if any((not o.is_leaf) or o.grad is not None or _has_hooks(o) for o in owners):
-        return None                  # a non-leaf "owner" feeds further autograd nodes right away
-    q = _ReduceQueue.tasks.get(task)
-    if q is None:
-        q = _ReduceQueue.tasks[task] = {"jobs": [], "table_jobs": [], "wgrad_jobs": [], "owners": set()}
-        _ReduceQueue.trim(_ReduceQueue.tasks)
-        torch.autograd.Variable._execution_engine.queue_callback(lambda: flush_reductions(task))
-    keys = [o.data_ptr() for o in owners]
-    if any(k in q["owners"] for k in keys):
-        _launch_queue(q)             # second gradient of a parameter in one pass: autograd adds it to the first one now
-        return None
-    q["owners"].update(keys)
-    return q
-
-
-def flush_if_pending(owners=()):
-    """A gradient of `owners` is about to be returned to autograd WITHOUT going through the queue (a weight gradient small enough
-    for one launch): if an earlier use of the same parameter in this pass left a postponed (still unfilled) gradient in the queue,
-    autograd would add the two at once -- issue the queue first.  (A module applied to one large and one small input.)"""
-    if not _ReduceQueue.enabled:
-        return
-    q = _ReduceQueue.tasks.get(_graph_task_id())
-    if q is not None and any(o is not None and o.data_ptr() in q["owners"] for o in owners):
-        _launch_queue(q)
-
-
-def grad_slot(param):
-    """The flat-gradient-buffer view dp.GradReducer(pack=True) reserved for `param` (``param._grad_slot``) if this backward
-    pass may write the parameter's gradient straight into it: the parameter holds no gradient yet (nothing to accumulate
-    into), has no hooks, and the slot has not been handed out earlier in the same pass (a weight used twice gets a
-    private buffer the second time and autograd adds the two).  None otherwise."""
-    slot = getattr(param, "_grad_slot", None)
-    if slot is None or not param.is_leaf or param.grad is not None or slot.device != param.device or _has_hooks(param):
-        return None
-    task = _graph_task_id()
-    if task == -1:
-        return None
-    used = _ReduceQueue.slots.get(task)
-    if used is None:
-        used = _ReduceQueue.slots[task] = set()
-        _ReduceQueue.trim(_ReduceQueue.slots)
-    if slot.data_ptr() in used:
-        return None
-    used.add(slot.data_ptr())
-    return slot
-
-
-def sum_rows(src, rows, cols, ld=None, col_offset=0, out=None, owners=()):
-    """f32 [cols]: out[c] = sum_{r < rows} src.flatten()[r * ld + col_offset + c] in a fixed order (pswin_reduce_jobs).
-    owners: the parameters whose gradient the result is; inside a backward pass with set_deferred_reductions(True) the
-    launch is then postponed to the end of that pass when that is safe (_deferring).
-    out: an existing contiguous f32 buffer of `cols` elements to write (see grad_slot); a fresh view of it is returned."""
-    ld = cols if ld is None else ld
-    if not src.is_contiguous():
-        raise PswinError("sum_rows expects a contiguous source")
-    if out is not None:
-        if out.dtype != torch.float32 or out.numel() != cols or not out.is_contiguous():
-            raise PswinError("sum_rows: `out` must be a contiguous float32 buffer of `cols` elements")
-        job = (src, col_offset * src.element_size(), dtype_code(src), rows, cols, ld, out)
-        q = _deferring(owners)
-        if q is not None:
-            q["jobs"].append(job)
-        else:
-            _launch_reductions([job])
-        return out.view(cols)
-    out = torch.empty(cols, dtype=torch.float32, device=src.device)
-    job = (src, col_offset * src.element_size(), dtype_code(src), rows, cols, ld, out)
-    q = _deferring(owners)
-    if q is None:
-        _launch_reductions([job])
-        return out
-    q["jobs"].append(job)
-    # the queue keeps `out` alive until the launch; hand autograd a fresh view so that AccumulateGrad can still adopt
-    # the buffer as param.grad (it clones tensors that have other owners)
-    return out.view(cols)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -873,7 +664,6 @@ def gemm_nt_rows(M, N):
 
 def transpose_weights(pairs):
     """dst = src^T for every (src [R, C], dst [C, R]) pair of contiguous bf16 matrices, one launch (pswin_transpose_jobs)."""
-    import ctypes
     if not pairs:
         return
     arr = (_lib.TransposeJob * len(pairs))()
@@ -916,9 +706,9 @@ def queue_weight_gradient(dy, x, weight, bias, zero_cols):
     ends -- or None = launch now.  The operands stay referenced by the queue until then."""
     M, N = dy.shape
     K = x.shape[1]
-    if not (GROUPED_WGRAD and _ReduceQueue.enabled and dy.dtype == torch.bfloat16 and gemm_tn_ring_splits(M, N, K) > 0):
+    if not (GROUPED_WGRAD and dy.dtype == torch.bfloat16 and gemm_tn_ring_splits(M, N, K) > 0):
         return None
-    q = _deferring((weight, bias))
+    q = grad_queue.deferring((weight, bias))              # None as well when deferral is off
     if q is None:
         return None
     splits = grouped_wgrad_splits(M)
@@ -930,16 +720,16 @@ def queue_weight_gradient(dy, x, weight, bias, zero_cols):
         part = out                                        # the finished f32 gradient straight from the kernel: nothing to reduce
     else:
         part = torch.empty(splits, N, K, dtype=torch.bfloat16 if GEMM_TN_RING_BF16 else torch.float32, device=dev)
-        q["jobs"].append((part, 0, dtype_code(part), splits, N * K, N * K, out))
+        q.add_reduction(part, splits, N * K, out)
     dbp = db = None
     if bias is not None:
         db = torch.empty(N, dtype=torch.float32, device=dev)
         dbp = db if splits == 1 else torch.empty(splits, N, dtype=torch.float32, device=dev)
         if splits > 1:
-            q["jobs"].append((dbp, 0, F32, splits, N, N, db))
+            q.add_reduction(dbp, splits, N, db)
         db = db.view(N)                                   # fresh views: see sum_rows
     zlo, zhi = (0, 0) if zero_cols is None else (int(zero_cols[0]), int(zero_cols[1]))
-    q["wgrad_jobs"].append((dy, x, part, dbp, M, N, K, splits, zlo, zhi))
+    q.add_weight_gradient(dy, x, part, dbp, splits, zlo, zhi)
     return out.view(N, K), db
 
 
@@ -1500,7 +1290,6 @@ class _WindowAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q_or_qkv, k, v, alpha, beta, dist, mask, heads, scale, n_bias_windows, chunks):
-        import ctypes
         fused = k is None
         x = q_or_qkv.contiguous()
         C = heads * _lib.HEAD_DIM
@@ -1548,7 +1337,6 @@ def attention_backward(x, k, v, lse, alpha, beta, dist, mask, dout, heads, scale
     None) or q with separate k, v; packed=True: x = [n, heads, 3, 49, 32] (what the fused forward kernel saves), the
     gradient still comes back as one row-major [rows, 3C] tensor.  Returns (dx, dk, dv, dalpha, dbeta); owners = the
     (alpha, beta) parameters."""
-    import ctypes
     C = heads * _lib.HEAD_DIM
     n = x.shape[0] if packed else x.shape[0] // WTOK
     fused = k is None
@@ -1588,28 +1376,8 @@ def attention_backward(x, k, v, lse, alpha, beta, dist, mask, dout, heads, scale
          chunks, n, nb, heads, scale, dtype_code(x),
          algo_bytes=n * heads * 7 * WTOK * _lib.HEAD_DIM * x.element_size())
     if need_tables:
-        dbeta = torch.empty(169, heads, dtype=torch.float32, device=x.device)
-        dalpha = torch.empty_like(dbeta) if dist is not None else None
-        ws = torch.empty(lib.pswin_attn_table_grads_workspace(heads), dtype=torch.float32, device=x.device)
-        job = (gsum, None if dist is None else dist.bwd, dalpha, dbeta, ws, chunks * nb, nb,
-               0 if dist is None else dist.n, heads)
-        # with deferred reductions the whole table gradient waits for the end of the pass: ONE launch sums the dScore tiles of all
-        # attention modules (round 4: twelve launches of 9-15 us per step were mostly ramp; the tiles -- 16 KB per work item and head,
-        # ~190 MB per PanoSwin-T step at batch 8 -- stay referenced by the queue until then), the sum of its partial rows joins the grouped
-        # reduction and ONE binning launch follows (same kernels, same per-module decomposition either way: bitwise equal results)
-        ld = ws.numel() // 129
-        rjob = (ws, 0, F32, lib.pswin_attn_table_grads_partial_rows(chunks * nb, heads), ld, ld, ws[128 * ld:])
-        q = _deferring(owners)
-        if q is None or not DEFER_TABLE_PARTIALS:
-            _launch_table_grads([job], 1)
-        if q is not None:
-            q["jobs"].append(rjob)
-            q["table_jobs"].append(job)
-            dbeta = dbeta.view(169, heads)                       # fresh views: see sum_rows
-            dalpha = None if dalpha is None else dalpha.view(169, heads)
-        else:
-            _launch_reductions([rjob])
-            _launch_table_grads([job], 4)
+        dalpha, dbeta = grad_queue.table_gradients(gsum, None if dist is None else dist.bwd, chunks * nb, nb, 0 if dist is None else dist.n,
+                                                   heads, owners, DEFER_TABLE_PARTIALS)
     return dx, dk, dv, dalpha, dbeta
 
 
@@ -1712,7 +1480,6 @@ def _roi_levels(ptrs_fwd, ptrs_bwd, shapes, strides):
 class _RoiAlignFPN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rois, roi_level, P, sampling_ratio, aligned, strides, *feats):
-        import ctypes
         C = feats[0].shape[1]
         dt = feats[0].dtype
         if len(feats) > 4 or any(f.dtype != dt or f.shape[1] != C or f.dim() != 4 for f in feats):
@@ -1734,7 +1501,6 @@ class _RoiAlignFPN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        import ctypes
         rois, roi_level = ctx.saved_tensors
         P, sr, aligned, strides, shapes, batches, C, dt = ctx.cfg
         d = dout.permute(0, 2, 3, 1).to(dt).contiguous()                    # [R, P, P, C]
@@ -1765,7 +1531,6 @@ _NMS_COUNTS = {}
 def nms_groups(box_list, iou_thr):
     """Greedy NMS of several score-sorted box lists in ONE launch (pswin_nms_groups; a workgroup per list): list of bool keep masks.
     box_list: f32 [n_g, 4] tensors on one HIP device, n_g <= 2048 (the RPN's nms_pre = 2000 per image and pyramid level)."""
-    import ctypes
     ns = tuple(int(b.shape[0]) for b in box_list)
     dev = box_list[0].device
     nmax = -(-max(ns) // 64) * 64                    # the kernels work on whole 64-row chunks

@@ -180,7 +180,7 @@ def test_deferred_reductions_with_activation_checkpointing():
     """use_checkpoint=True makes every block's backward a nested autograd pass; each pass must flush its own queued
     reductions (the queue is keyed by graph task): same parameter gradients as the immediate mode, bit for bit."""
     import panoswintransformerobjectdetection_amd as pkg
-    from panoswintransformerobjectdetection_amd import ops
+    from panoswintransformerobjectdetection_amd import grad_queue, ops
     cfg = dict(TINY, drop_path_rate=0.0, use_checkpoint=True)
     torch.manual_seed(0)
     m = pkg.SimplePanoSwinTransformer(**cfg, compute_dtype=torch.bfloat16).to(DEV).train()
@@ -199,7 +199,7 @@ def test_deferred_reductions_with_activation_checkpointing():
         got = grads()
     finally:
         ops.set_deferred_reductions(prev)
-    assert not ops._ReduceQueue.tasks
+    assert not grad_queue.pending()
     assert ref.keys() == got.keys() and len(ref) > 50
     for k in ref:
         if k.startswith("patch_embed"):      # this small stem runs on library convolutions (not run-to-run bitwise stable)
@@ -237,7 +237,7 @@ def test_hipgraph_replay_matches_eager():
     assert all(torch.isfinite(g).all() for g in gref.values())
     # the captured step also postpones the ~120 parameter-gradient reductions to ONE grouped launch at the end of the
     # backward pass (ops.set_deferred_reductions); same kernel, same summation order: still bit-identical
-    from panoswintransformerobjectdetection_amd import ops
+    from panoswintransformerobjectdetection_amd import grad_queue, ops
     prev = ops.set_deferred_reductions(True)
     try:
         eager_deferred = [t.detach().clone() for t in step()]
@@ -253,7 +253,7 @@ def test_hipgraph_replay_matches_eager():
                 assert torch.equal(p.grad, gref[k]), k
     finally:
         ops.set_deferred_reductions(prev)
-    assert not ops._ReduceQueue.tasks
+    assert not grad_queue.pending()
     del eager_deferred
 
 
@@ -334,7 +334,7 @@ def test_deferred_reductions_stay_correct_when_a_result_is_read_before_the_pass_
     the pass ends.  Three cases that would otherwise add or clone unwritten memory: a Linear applied twice in one pass
     (autograd adds the two gradients when the second arrives), accumulation into an existing .grad over two passes, and a
     parameter with a post-accumulate hook (what dp.GradReducer(pack=False) registers)."""
-    from panoswintransformerobjectdetection_amd import ops
+    from panoswintransformerobjectdetection_amd import grad_queue, ops
     from panoswintransformerobjectdetection_amd.backbone import _linear
     torch.manual_seed(0)
     lin = torch.nn.Linear(64, 64).to(DEV)
@@ -368,7 +368,7 @@ def test_deferred_reductions_stay_correct_when_a_result_is_read_before_the_pass_
             got, got_seen = run(passes, hook)
         finally:
             ops.set_deferred_reductions(prev)
-        assert not ops._ReduceQueue.tasks
+        assert not grad_queue.pending()
         for a, b in zip(ref, got):
             assert torch.isfinite(b).all() and torch.equal(a, b), (passes, hook)
         for a, b in zip(ref_seen, got_seen):        # what a hook sees at accumulation time is already the final value

@@ -401,6 +401,7 @@ def test_grouped_reduction_many_jobs(ops):
     """pswin_reduce_jobs: 230 independent column sums (3 launches of <= 96 jobs) with every block shape (1 / 8 / 64 row
     lanes), both source dtypes, row strides larger than the summed width and a column offset, against float64 sums."""
     import random
+    from panoswintransformerobjectdetection_amd import grad_queue
     rnd = random.Random(7)
     jobs, want = [], []
     for i in range(230):
@@ -412,19 +413,19 @@ def test_grouped_reduction_many_jobs(ops):
         off = ve * rnd.choice([0, 1]) if pad else 0
         ld = cols + pad
         src = (det_uniform((rows, ld), f"rj{i}") * 2).to(dt).to(DEV)
-        jobs.append((src, off * src.element_size(), 1 if dt == torch.bfloat16 else 0, rows, cols, ld,
-                     torch.full((cols,), float("nan"), device=DEV)))
+        jobs.append(grad_queue.Reduction(src, off * src.element_size(), 1 if dt == torch.bfloat16 else 0, rows, cols, ld,
+                                         torch.full((cols,), float("nan"), device=DEV)))
         want.append(src.double()[:, off:off + cols].sum(0))
-    ops._launch_reductions(jobs)
+    grad_queue._launch_reductions(jobs)
     torch.cuda.synchronize()
     for j, w in zip(jobs, want):
-        assert torch.allclose(j[6].double(), w, rtol=1e-5, atol=1e-4), (j[3], j[4], j[5])
+        assert torch.allclose(j.dst.double(), w, rtol=1e-5, atol=1e-4), (j.rows, j.cols, j.ld)
 
 
 def test_table_grads_batch_matches_single_jobs(ops):
     """pswin_attn_table_grads_batch over three modules with different head counts / tile counts (with and without the
     great-circle table) == the same jobs issued one by one, and == a float64 evaluation of the definition."""
-    from panoswintransformerobjectdetection_amd import _lib
+    from panoswintransformerobjectdetection_amd import _lib, grad_queue
     lib = _lib.load()
     idx = torch.tensor([[(i // 7 - j // 7 + 6) * 13 + (i % 7 - j % 7 + 6) for i in range(49)] for j in range(49)])  # [j][i]
     jobs, want = [], []
@@ -438,7 +439,7 @@ def test_table_grads_batch_matches_single_jobs(ops):
         dbeta = torch.full((169, heads), float("nan"), device=DEV)
         dalpha = torch.full((169, heads), float("nan"), device=DEV) if n_dist else None
         ws = torch.empty(lib.pswin_attn_table_grads_workspace(heads), device=DEV)
-        jobs.append((g.to(DEV), None if dist is None else dist.to(DEV), dalpha, dbeta, ws, n_tiles, nb, n_dist, heads))
+        jobs.append(grad_queue.TableGrad(g.to(DEV), None if dist is None else dist.to(DEV), dalpha, dbeta, ws, n_tiles, nb, n_dist, heads))
         gs = g[:, :, :49, :49].double()
         wb = torch.zeros(169, heads, dtype=torch.float64)
         wb.index_add_(0, idx.flatten(), gs.sum(0).permute(1, 2, 0).reshape(49 * 49, heads))
@@ -448,17 +449,17 @@ def test_table_grads_batch_matches_single_jobs(ops):
             wa = torch.zeros(169, heads, dtype=torch.float64)
             wa.index_add_(0, idx.flatten(), (gs * d[:, None]).sum(0).permute(1, 2, 0).reshape(49 * 49, heads))
         want.append((wa, wb))
-    ops._launch_table_grads(jobs)
+    grad_queue._launch_table_grads(jobs)
     torch.cuda.synchronize()
-    batch = [(None if j[2] is None else j[2].clone(), j[3].clone()) for j in jobs]
+    batch = [(None if j.dalpha is None else j.dalpha.clone(), j.dbeta.clone()) for j in jobs]
     for j, (ba, bb), (wa, wb) in zip(jobs, batch, want):
         assert torch.allclose(bb.double().cpu(), wb, rtol=1e-5, atol=1e-4)
         if wa is not None:
             assert torch.allclose(ba.double().cpu(), wa, rtol=1e-5, atol=1e-4)
-        j[3].fill_(float("nan"))
-        ops._launch_table_grads([j])
+        j.dbeta.fill_(float("nan"))
+        grad_queue._launch_table_grads([j])
         torch.cuda.synchronize()
-        assert torch.equal(j[3], bb) and (ba is None or torch.equal(j[2], ba))
+        assert torch.equal(j.dbeta, bb) and (ba is None or torch.equal(j.dalpha, ba))
 
 
 def test_rejects_cpu_and_bad_args(ops):
@@ -998,7 +999,7 @@ def test_gemm_tn_ring_jobs_one_launch_equals_the_single_launches(ops):
     (first_wg padding to multiples of 8, the binary search over the job table, longest-first ordering on the Python side are all in
     play): every partial slab and bias partial must equal the single launch of the same product BIT FOR BIT, and the sums an fp32 matmul."""
     import ctypes
-    from panoswintransformerobjectdetection_amd import _lib
+    from panoswintransformerobjectdetection_amd import _lib, grad_queue
     lib = _lib.load()
     torch.manual_seed(7)
     spec = [(19600, 1152, 384, 9, True, True), (4096, 768, 3072, 2, True, False), (1470, 2304, 768, 1, False, True), (333, 192, 192, 3, False, False),
@@ -1016,16 +1017,16 @@ def test_gemm_tn_ring_jobs_one_launch_equals_the_single_launches(ops):
             part1, db1 = ops.gemm_tn_ring(dy, x, sp, pdt), None
         part = torch.full_like(part1, float("nan"))
         dbp = torch.full_like(db1, float("nan")) if with_bias else None
-        jobs.append((dy, x, part, dbp, M, N, K, sp, zc[0] if zc else 0, zc[1] if zc else 0))
+        jobs.append(grad_queue.WeightGrad(dy, x, part, dbp, M, N, K, sp, zc[0] if zc else 0, zc[1] if zc else 0))
         singles.append((part1, db1))
-    ops._launch_wgrads(jobs)
+    grad_queue._launch_wgrads(jobs)
     torch.cuda.synchronize()
-    for (dy, x, part, dbp, M, N, K, sp, zlo, zhi), (part1, db1) in zip(jobs, singles):
-        assert torch.equal(part, part1), (M, N, K, sp)
-        if dbp is not None:
-            assert torch.equal(dbp, db1), (M, N, K, sp)
-        ref = dy.float().t() @ x.float()
-        assert torch.allclose(part.float().sum(0), ref, rtol=6e-3, atol=6e-3 * float(ref.abs().max()))
+    for j, (part1, db1) in zip(jobs, singles):
+        assert torch.equal(j.partial, part1), (j.M, j.N, j.K, j.splits)
+        if j.dbias_partial is not None:
+            assert torch.equal(j.dbias_partial, db1), (j.M, j.N, j.K, j.splits)
+        ref = j.dy.float().t() @ j.x.float()
+        assert torch.allclose(j.partial.float().sum(0), ref, rtol=6e-3, atol=6e-3 * float(ref.abs().max()))
     # argument errors never launch
     bad = (_lib.TnJob * 1)()
     bad[0].dy, bad[0].x, bad[0].partial, bad[0].M, bad[0].N, bad[0].K, bad[0].splits, bad[0].partial_dtype = 16, 16, 16, 4096, 200, 192, 1, 0
@@ -1037,6 +1038,7 @@ def test_grouped_weight_gradients_are_bit_equal_to_immediate_ones(ops):
     """ops.queue_weight_gradient: with deferred reductions a Linear's weight (and bias) gradient is produced by the grouped end-of-pass
     launch; same split rule, kernel and summation order as the launch-where-produced mode, so the two agree bit for bit, and both with
     fp32 autograd of the same bf16 operands."""
+    from panoswintransformerobjectdetection_amd import grad_queue
     from panoswintransformerobjectdetection_amd.backbone import _linear
     torch.manual_seed(3)
     lins = [torch.nn.Linear(192, 576).to(DEV), torch.nn.Linear(576, 192).to(DEV), torch.nn.Linear(192, 384, bias=False).to(DEV)]
@@ -1060,7 +1062,7 @@ def test_grouped_weight_gradients_are_bit_equal_to_immediate_ones(ops):
         got = run()
     finally:
         ops.set_deferred_reductions(prev)
-    assert not ops._ReduceQueue.tasks
+    assert not grad_queue.pending()
     for a, b in zip(ref, got):
         assert torch.isfinite(b).all() and torch.equal(a, b)
     # against autograd on fp32 copies of the bf16-rounded operands (loose: bf16 activations in between)
