@@ -729,6 +729,21 @@ int pswin_pano_warp_u8(const uint8_t* src, const double* params, uint8_t* dst, i
 int pswin_pano_resize_normalize_pad(const uint8_t* src, const int32_t* out_hw, const float* norm, int to_rgb, float* dst, int B, int H,
                                     int W, int Hp, int Wp, void* stream);
 
+/* The recipe's AutoAugment (configs/swin/faster_rcnn_panoswin_tiny_patch4_window7_mstrain_480800_adamw_1x_streetwin.py:65-89) with
+ * Normalize + Pad + collate, in one launch without a scratch buffer: per image either policy 0, Resize (mmdet/datasets/pipelines/
+ * transforms.py:212-242, 289-330), or policy 1, Resize -> RandomCrop (transforms.py:840-876, 960-975) -> Resize(override=True).
+ * plan: int32 [B, 8] on the DEVICE, per image (h1, w1, cy, cx, ch, cw, oh, ow).  "resize" is the float32 resize of
+ * pswin_pano_resize_normalize_pad, rounded half-up to uint8.
+ *   h1 <= 0: dst[b] is what pswin_pano_resize_normalize_pad writes for out_hw[b] = (oh, ow), bit for bit;
+ *   h1 >  0: I = resize(src[b], h1 x w1) as uint8, K = I[cy:cy+ch, cx:cx+cw], u = resize(K, oh x ow) -- the replicated border is the
+ *            crop's border -- then (u - norm[c]) * norm[3 + c] with the channel swap of to_rgb, and 0 outside oh x ow up to Hp x Wp.
+ * I and K are never stored: a workgroup computes the pixels of I its output tile reads into LDS, or, where the second resize shrinks
+ * by more than about 2, each thread computes its own; both give the same bits.  The plan is clamped on the device (a captured graph
+ * replays with whatever the buffer holds): oh, ow to [0, Hp] x [0, Wp], w1 to >= 1, cy to [0, h1-1], ch to [1, h1-cy], cx to
+ * [0, w1-1], cw to [1, w1-cx].  src, norm, dst, to_rgb: as pswin_pano_resize_normalize_pad. */
+int pswin_pano_resize_crop_resize_normalize_pad(const uint8_t* src, const int32_t* plan, const float* norm, int to_rgb, float* dst, int B,
+                                                int H, int W, int Hp, int Wp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

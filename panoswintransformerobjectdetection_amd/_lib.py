@@ -127,6 +127,7 @@ _PROTOTYPES = {
     "pswin_attn_table_grads": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "pswin_pano_warp_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "pswin_pano_resize_normalize_pad": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "pswin_pano_resize_crop_resize_normalize_pad": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
 }
 
 _lib = None

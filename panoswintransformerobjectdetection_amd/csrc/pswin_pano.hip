@@ -1,5 +1,6 @@
-// Panorama training augmentation on the device: PanoStretch + RollAug + RandomFlip in one gather (pswin_pano_warp_u8) and
-// Resize + Normalize + Pad into the backbone's input in a second one (pswin_pano_resize_normalize_pad).
+// Panorama training augmentation on the device: PanoStretch + RollAug + RandomFlip in one gather (pswin_pano_warp_u8),
+// Resize + Normalize + Pad into the backbone's input in a second one (pswin_pano_resize_normalize_pad), and the Resize -> RandomCrop ->
+// Resize policy of the recipe's AutoAugment in the place of that resize (pswin_pano_resize_crop_resize_normalize_pad).
 //
 // Reference: PanoStretch / RollAug (mmdet/datasets/pipelines/transforms.py:992-1068) call lzx/yolo/extensions/xzaug.py getAug,
 // which resamples with scipy.ndimage.map_coordinates(order=1, mode='wrap') on float64 coordinates, and rollaug.py roll_aug_raw
@@ -169,6 +170,69 @@ __global__ __launch_bounds__(PANO_TX* PANO_TY) void pano_warp_kernel(const unsig
     }
 }
 
+// One axis of the bilinear resize n_in -> n_out (scale = (float)n_in / (float)n_out) at output index d: the two source indices and
+// their weights.  float32, align_corners=False geometry, source coordinate clamped at 0, last row / column replicated.
+__device__ inline void resize_tap(float scale, int d, int n_in, int& i0, int& i1, float& l0, float& l1) {
+    float f = scale * ((float)d + 0.5f) - 0.5f;
+    f = f < 0.f ? 0.f : f;
+    i0 = (int)f < n_in - 1 ? (int)f : n_in - 1;
+    i1 = i0 < n_in - 1 ? i0 + 1 : i0;
+    l1 = f - (float)i0;
+    l0 = 1.f - l1;
+}
+
+// The one blend expression of every resize here: four taps, rounded half-up to a uint8 value held in a float.  The library builds
+// with -ffp-contract=off, so every use of it rounds alike.
+__device__ inline float blend_round(float ly0, float ly1, float lx0, float lx1, float v00, float v01, float v10, float v11) {
+    const float t = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+    float u = floorf(t + 0.5f);
+    return u < 0.f ? 0.f : (u > 255.f ? 255.f : u);
+}
+
+__device__ inline float normalise(float u, float mean, float inv_std) { return (u - mean) * inv_std; }
+
+// Output row y, columns x .. x+3 of the resize of img (uint8 [H, W, 3]) to oh x ow, normalised, output channel c = source channel
+// (to_rgb ? 2 - c : c).  Columns at or past ow keep what `out` holds.
+__device__ inline void resize_px4(const unsigned char* __restrict__ img, int H, int W, int oh, int ow, int y, int x, int to_rgb,
+                                  const float* __restrict__ norm, float (&out)[3][PANO_PX]) {
+    int y0, y1;
+    float ly0, ly1;
+    resize_tap((float)H / (float)oh, y, H, y0, y1, ly0, ly1);
+    const unsigned char* r0 = img + (size_t)y0 * W * 3;
+    const unsigned char* r1 = img + (size_t)y1 * W * 3;
+    const float sw = (float)W / (float)ow;
+#pragma unroll
+    for (int j = 0; j < PANO_PX; ++j) {
+        if (x + j < ow) {
+            int x0, x1;
+            float lx0, lx1;
+            resize_tap(sw, x + j, W, x0, x1, lx0, lx1);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int sc = to_rgb ? 2 - c : c;
+                const float v00 = (float)r0[(size_t)x0 * 3 + sc], v01 = (float)r0[(size_t)x1 * 3 + sc];
+                const float v10 = (float)r1[(size_t)x0 * 3 + sc], v11 = (float)r1[(size_t)x1 * 3 + sc];
+                out[c][j] = normalise(blend_round(ly0, ly1, lx0, lx1, v00, v01, v10, v11), norm[c], norm[3 + c]);
+            }
+        }
+    }
+}
+
+// Row y, columns x .. x+3 of the three output planes of image b: one 128-bit store per plane when the row allows it.
+__device__ inline void store_planes(float* __restrict__ dst, int b, int y, int x, int Hp, int Wp, int vec, const float (&out)[3][PANO_PX]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float* row = dst + (((size_t)b * 3 + c) * Hp + y) * Wp;
+        if (vec && x + PANO_PX <= Wp) {
+            *reinterpret_cast<f32x4*>(row + x) = f32x4{out[c][0], out[c][1], out[c][2], out[c][3]};
+        } else {
+#pragma unroll
+            for (int j = 0; j < PANO_PX; ++j)
+                if (x + j < Wp) row[x + j] = out[c][j];
+        }
+    }
+}
+
 // grid (ceil(Wp / 256), ceil(Hp / 4), B), block (64, 4): each thread writes 4 consecutive columns of one row in all 3 planes.
 // Inside the image's own size (out_hw[b]) the pixel is the bilinear resize (float32, align_corners=False geometry, source index
 // clamped at 0, last row / column replicated) rounded half-up to uint8, then (v - mean) * (1 / std); outside it is 0.
@@ -187,50 +251,119 @@ __global__ __launch_bounds__(PANO_TX* PANO_TY) void pano_resize_kernel(const uns
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int j = 0; j < PANO_PX; ++j) out[c][j] = 0.f;
-    if (y < oh && x < ow) {
-        const float sh = (float)H / (float)oh;
-        float fy = sh * ((float)y + 0.5f) - 0.5f;
-        fy = fy < 0.f ? 0.f : fy;
-        const int y0 = (int)fy < H - 1 ? (int)fy : H - 1;
-        const int y1 = y0 < H - 1 ? y0 + 1 : y0;
-        const float ly1 = fy - (float)y0;
-        const float ly0 = 1.f - ly1;
-        const unsigned char* r0 = src + ((size_t)b * H + y0) * W * 3;
-        const unsigned char* r1 = src + ((size_t)b * H + y1) * W * 3;
-        const float sw = (float)W / (float)ow;
+    if (y < oh && x < ow) resize_px4(src + (size_t)b * H * W * 3, H, W, oh, ow, y, x, to_rgb, norm, out);
+    store_planes(dst, b, y, x, Hp, Wp, vec, out);
+}
+
+// ---- Resize -> RandomCrop -> Resize (the second policy of the recipe's AutoAugment) in one launch --------------------------------
+//
+// I = resize(src, h1 x w1) as uint8, K = I[cy:cy+ch, cx:cx+cw], out = resize(K, oh x ow); neither I nor K is ever stored in memory.
+// A workgroup's 4 x 256 output tile reads the rectangle rows r0..r1, columns c0..c1 of K; when that fits RCR_ROWS x RCR_COLS the
+// workgroup computes those pixels of I once into LDS (one 32-bit word per pixel: the three source channels in bytes 0..2) and
+// resizes out of LDS; otherwise every thread computes the four intermediate pixels of each output pixel itself.  Both paths call
+// inter_px and crop_resize_px4, so they give the same bits.
+constexpr int RCR_ROWS = 10;                     // 4 output rows at a shrink factor of 2, plus the second tap and the phase
+constexpr int RCR_COLS = 2 * PANO_COLS + 2;
+
+// Pixel (iy, ix) of I = resize(img, h1 x w1): the three source channels packed into bytes 0..2.
+__device__ inline unsigned int inter_px(const unsigned char* __restrict__ img, int H, int W, int h1, int w1, int iy, int ix) {
+    int y0, y1, x0, x1;
+    float ly0, ly1, lx0, lx1;
+    resize_tap((float)H / (float)h1, iy, H, y0, y1, ly0, ly1);
+    resize_tap((float)W / (float)w1, ix, W, x0, x1, lx0, lx1);
+    const unsigned char* r0 = img + (size_t)y0 * W * 3;
+    const unsigned char* r1 = img + (size_t)y1 * W * 3;
+    unsigned int p = 0;
 #pragma unroll
-        for (int j = 0; j < PANO_PX; ++j) {
-            if (x + j < ow) {
-                float fx = sw * ((float)(x + j) + 0.5f) - 0.5f;
-                fx = fx < 0.f ? 0.f : fx;
-                const int x0 = (int)fx < W - 1 ? (int)fx : W - 1;
-                const int x1 = x0 < W - 1 ? x0 + 1 : x0;
-                const float lx1 = fx - (float)x0;
-                const float lx0 = 1.f - lx1;
+    for (int c = 0; c < 3; ++c) {
+        const float v00 = (float)r0[(size_t)x0 * 3 + c], v01 = (float)r0[(size_t)x1 * 3 + c];
+        const float v10 = (float)r1[(size_t)x0 * 3 + c], v11 = (float)r1[(size_t)x1 * 3 + c];
+        p |= (unsigned int)blend_round(ly0, ly1, lx0, lx1, v00, v01, v10, v11) << (8 * c);
+    }
+    return p;
+}
+
+// resize_px4 on the crop K (ch x cw): px(ky, kx) returns the packed pixel of K.
+template <class Fetch>
+__device__ inline void crop_resize_px4(Fetch px, int ch, int cw, int oh, int ow, int y, int x, int to_rgb, const float* __restrict__ norm,
+                                       float (&out)[3][PANO_PX]) {
+    int y0, y1;
+    float ly0, ly1;
+    resize_tap((float)ch / (float)oh, y, ch, y0, y1, ly0, ly1);
+    const float sw = (float)cw / (float)ow;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int sc = to_rgb ? 2 - c : c;
-                    const float v00 = (float)r0[(size_t)x0 * 3 + sc], v01 = (float)r0[(size_t)x1 * 3 + sc];
-                    const float v10 = (float)r1[(size_t)x0 * 3 + sc], v11 = (float)r1[(size_t)x1 * 3 + sc];
-                    const float t = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
-                    float u = floorf(t + 0.5f);
-                    u = u < 0.f ? 0.f : (u > 255.f ? 255.f : u);
-                    out[c][j] = (u - norm[c]) * norm[3 + c];
-                }
+    for (int j = 0; j < PANO_PX; ++j) {
+        if (x + j < ow) {
+            int x0, x1;
+            float lx0, lx1;
+            resize_tap(sw, x + j, cw, x0, x1, lx0, lx1);
+            const unsigned int p00 = px(y0, x0), p01 = px(y0, x1), p10 = px(y1, x0), p11 = px(y1, x1);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int sh = 8 * (to_rgb ? 2 - c : c);
+                const float v00 = (float)((p00 >> sh) & 255u), v01 = (float)((p01 >> sh) & 255u);
+                const float v10 = (float)((p10 >> sh) & 255u), v11 = (float)((p11 >> sh) & 255u);
+                out[c][j] = normalise(blend_round(ly0, ly1, lx0, lx1, v00, v01, v10, v11), norm[c], norm[3 + c]);
             }
         }
     }
+}
+
+__device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Grid and block of pano_resize_kernel.  plan[b] = (h1, w1, cy, cx, ch, cw, oh, ow); h1 <= 0: the plain resize H x W -> oh x ow.
+// No thread returns before the barrier: every branch that holds it depends on plan[b] and the block index alone.
+__global__ __launch_bounds__(PANO_TX* PANO_TY) void pano_rcr_kernel(const unsigned char* __restrict__ src, int H, int W,
+                                                                     const int32_t* __restrict__ plan, const float* __restrict__ norm,
+                                                                     int to_rgb, float* __restrict__ dst, int Hp, int Wp, int vec) {
+    __shared__ unsigned int s_tile[RCR_ROWS * RCR_COLS];
+    const int b = blockIdx.z;
+    const int ty0 = blockIdx.y * PANO_TY, tx0 = blockIdx.x * PANO_COLS;
+    const int y = ty0 + threadIdx.y;
+    const int x = tx0 + threadIdx.x * PANO_PX;
+    const int32_t* p = plan + 8 * b;
+    const int h1 = p[0];
+    const int oh = clampi(p[6], 0, Hp), ow = clampi(p[7], 0, Wp);
+    const bool inside = y < oh && x < ow;
+    const unsigned char* img = src + (size_t)b * H * W * 3;
+    float out[3][PANO_PX];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float* row = dst + (((size_t)b * 3 + c) * Hp + y) * Wp;
-        if (vec && x + PANO_PX <= Wp) {
-            *reinterpret_cast<f32x4*>(row + x) = f32x4{out[c][0], out[c][1], out[c][2], out[c][3]};
-        } else {
+    for (int c = 0; c < 3; ++c)
 #pragma unroll
-            for (int j = 0; j < PANO_PX; ++j)
-                if (x + j < Wp) row[x + j] = out[c][j];
+        for (int j = 0; j < PANO_PX; ++j) out[c][j] = 0.f;
+    if (h1 <= 0) {
+        if (inside) resize_px4(img, H, W, oh, ow, y, x, to_rgb, norm, out);
+    } else if (ty0 < oh && tx0 < ow) {
+        const int w1 = p[1] < 1 ? 1 : p[1];
+        const int cy = clampi(p[2], 0, h1 - 1), cx = clampi(p[3], 0, w1 - 1);
+        const int ch = clampi(p[4], 1, h1 - cy), cw = clampi(p[5], 1, w1 - cx);
+        // the rectangle of K this tile reads: resize_tap is monotone in the output index, so the first and the last output row
+        // (column) inside oh x ow bound the taps of every thread of the block
+        const int ylast = ty0 + PANO_TY - 1 < oh - 1 ? ty0 + PANO_TY - 1 : oh - 1;
+        const int xlast = tx0 + PANO_COLS - 1 < ow - 1 ? tx0 + PANO_COLS - 1 : ow - 1;
+        int r0, r1, c0, c1, i;
+        float l0, l1;
+        resize_tap((float)ch / (float)oh, ty0, ch, r0, i, l0, l1);
+        resize_tap((float)ch / (float)oh, ylast, ch, i, r1, l0, l1);
+        resize_tap((float)cw / (float)ow, tx0, cw, c0, i, l0, l1);
+        resize_tap((float)cw / (float)ow, xlast, cw, i, c1, l0, l1);
+        const int rh = r1 - r0 + 1, rw = c1 - c0 + 1;
+        if (rh <= RCR_ROWS && rw <= RCR_COLS) {
+            const int tid = threadIdx.y * PANO_TX + threadIdx.x;
+            for (int k = tid; k < rh * rw; k += PANO_TX * PANO_TY) {
+                const int ry = k / rw, rx = k - ry * rw;
+                s_tile[ry * RCR_COLS + rx] = inter_px(img, H, W, h1, w1, cy + r0 + ry, cx + c0 + rx);
+            }
+            __syncthreads();
+            if (inside)
+                crop_resize_px4([&](int ky, int kx) { return s_tile[(ky - r0) * RCR_COLS + (kx - c0)]; }, ch, cw, oh, ow, y, x, to_rgb,
+                                norm, out);
+        } else if (inside) {
+            crop_resize_px4([&](int ky, int kx) { return inter_px(img, H, W, h1, w1, cy + ky, cx + kx); }, ch, cw, oh, ow, y, x, to_rgb,
+                            norm, out);
         }
     }
+    if (y < Hp && x < Wp) store_planes(dst, b, y, x, Hp, Wp, vec, out);
 }
 
 template <int C>
@@ -265,5 +398,17 @@ extern "C" int pswin_pano_resize_normalize_pad(const uint8_t* src, const int32_t
     dim3 grid((Wp + PANO_COLS - 1) / PANO_COLS, (Hp + PANO_TY - 1) / PANO_TY, B);
     hipLaunchKernelGGL(pano_resize_kernel, grid, dim3(PANO_TX, PANO_TY), 0, (hipStream_t)stream, src, H, W, out_hw, norm, to_rgb ? 1 : 0,
                        dst, Hp, Wp, vec);
+    PSWIN_LAUNCH_RET();
+}
+
+extern "C" int pswin_pano_resize_crop_resize_normalize_pad(const uint8_t* src, const int32_t* plan, const float* norm, int to_rgb, float* dst,
+                                                           int B, int H, int W, int Hp, int Wp, void* stream) {
+    PSWIN_CHECK_ARG(src != nullptr && plan != nullptr && norm != nullptr && dst != nullptr);
+    PSWIN_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && Hp > 0 && Wp > 0);
+    PSWIN_CHECK_ARG((Hp + PANO_TY - 1) / PANO_TY <= 65535);
+    const int vec = (Wp % 4 == 0 && ((uintptr_t)dst & 15) == 0) ? 1 : 0;
+    dim3 grid((Wp + PANO_COLS - 1) / PANO_COLS, (Hp + PANO_TY - 1) / PANO_TY, B);
+    hipLaunchKernelGGL(pano_rcr_kernel, grid, dim3(PANO_TX, PANO_TY), 0, (hipStream_t)stream, src, H, W, plan, norm, to_rgb ? 1 : 0, dst,
+                       Hp, Wp, vec);
     PSWIN_LAUNCH_RET();
 }

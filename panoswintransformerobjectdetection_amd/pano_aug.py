@@ -1,9 +1,9 @@
-"""PanoSwin's panorama training augmentation on the device: PanoStretch, RollAug, RandomFlip, Resize, Normalize and Pad.
+"""PanoSwin's panorama training augmentation on the device: PanoStretch, RollAug, RandomFlip, AutoAugment / Resize, Normalize and Pad.
 
 The reference runs these in its CPU data pipeline (configs/swin/faster_rcnn_panoswin_tiny_patch4_window7_mstrain_480800_adamw_1x_
-streetwin.py:62-66; PanoStretch and RollAug at mmdet/datasets/pipelines/transforms.py:992-1068, which call
+streetwin.py:62-91; PanoStretch and RollAug at mmdet/datasets/pipelines/transforms.py:992-1068, which call
 lzx/yolo/extensions/xzaug.py getAug / _xzaug, rollaug.py roll_aug_raw and padding2.py merge_adjbox).  Here the pixels go through two
-HIP kernels (csrc/pswin_pano.hip) and the boxes stay on the host in numpy, with the reference's dtypes, order and rounding.
+launches of HIP kernels (csrc/pswin_pano.hip) and the boxes stay on the host in numpy, with the reference's dtypes, order and rounding.
 
 Image contract: the warp (stretch, roll, flip) is byte-identical to the reference.  For output pixel (x, y) of an H x W image
 (W even: sin u = 0 at x = (W-1)/2 otherwise) the stretch samples the source at (refy, refx), in float64 and in this order:
@@ -46,6 +46,17 @@ border replicated) in float32 and rounded half-up.  This is NOT bit-exact to cv2
 uint8 image may differ from mmcv.imresize by 1 LSB.  Normalize is mmcv.imnormalize: BGR -> RGB, then (v - mean) * (1/std) in float32
 (mean and 1/std rounded to float32 first, as cv2 does with the scalar).  Pad writes zeros up to a multiple of size_divisor and to
 the largest image of the batch (mmdet Pad followed by collate).
+
+AutoAugment (PanoTrainTransform(auto_augment=STREETWIN_AUTO_AUGMENT); the streetwin config, lines 65-89, wraps its Resize in it): per
+image np.random.choice over the two policies, which consumes the stream like randint(0, 2).  Policy 0 is the Resize above.  Policy 1 is
+Resize(first scales) -> RandomCrop('absolute_range', (384, 600), allow_negative_crop=True) -> Resize(train scales, override=True); its
+draws, in order: randint(len(first scales)); crop_h = randint(min(h1, 384), min(h1, 600) + 1); crop_w from the SAME height-based
+range (transforms.py:948-950 passes h for both); offset_h = randint(0, max(h1 - crop_h, 0) + 1); offset_w likewise;
+randint(len(train scales)).  The crop taken is min(crop, dim) per axis (numpy slicing truncates).  A Resize with one scale draws
+nothing.  Pixels: pswin_pano_resize_crop_resize_normalize_pad does both resizes and the crop in one launch (the intermediate uint8
+image is never stored), so the uint8 stages may differ from cv2 by 1 LSB twice.  Boxes: resize_boxes -> crop_boxes (float32 subtract,
+clip to the crop, keep x2 > x1 and y2 > y1; an empty result is valid) -> resize_boxes on the crop's size.  pano_ratio_v is
+[y1 / h1, y2 / h1] of the crop (transforms.py:874, PanoCheck 1128-1132), [0.0, 1.0] without one.
 """
 import numpy as np
 import torch
@@ -60,6 +71,9 @@ TRAIN_RESIZE_SCALES = [(480, 1333), (512, 1333), (544, 1333), (576, 1333), (608,
                        (736, 1333), (768, 1333), (800, 1333)]
 IMG_NORM_MEAN = (123.675, 116.28, 103.53)
 IMG_NORM_STD = (58.395, 57.12, 57.375)
+# the second policy of that config's AutoAugment (lines 56, 74-88); the first policy and the last Resize use TRAIN_RESIZE_SCALES
+STREETWIN_AUTO_AUGMENT = dict(first_scales=[(400, 1333), (500, 1333), (600, 1333)], crop_size=(384, 600), crop_type="absolute_range")
+PLAN_KEYS = ("h1", "w1", "cy", "cx", "ch", "cw", "oh", "ow")
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -88,6 +102,48 @@ def draw_pano_params(batch, W, kxy=(2., 2.), stretch_chance=1., roll_chance=1., 
         if flip_ratio is not None:
             p["flip"][i] = rng.choice(2, p=[flip_ratio, 1 - flip_ratio]) == 0
     return p
+
+
+def draw_auto_augment(h, w, cfg, rng=np.random, img_scales=TRAIN_RESIZE_SCALES):
+    """One h x w image's AutoAugment policy and plan, with the reference's draws in the reference's order (module docstring).
+
+    cfg: STREETWIN_AUTO_AUGMENT or a dict of the same keys.  Returns a dict: policy (0 or 1), scale_idx and scale (the final Resize),
+    plan (h1, w1, cy, cx, ch, cw, oh, ow; all zero but oh, ow for policy 0), draws (every integer drawn, in order), crop ((y1, x1, y2,
+    x2) or None), pano_ratio_v, pano_lr_noadj (None without a crop: the reference leaves the key out), and for policy 1 first_idx,
+    first_scale, h1, w1, crop_h, crop_w (as drawn), offset_h, offset_w, ch, cw (as taken)."""
+    if cfg.get("crop_type", "absolute_range") != "absolute_range":
+        raise PswinError(f"draw_auto_augment: only crop_type 'absolute_range' is implemented, got {cfg.get('crop_type')!r}")
+    lo, hi = cfg["crop_size"]
+    if not (isinstance(lo, int) and isinstance(hi, int) and 0 < lo <= hi):
+        raise PswinError(f"draw_auto_augment: crop_size must be two positive ints (low, high), got {cfg['crop_size']}")
+    policy = int(rng.randint(0, 2))
+    draws = [policy]
+
+    def pick(scales):
+        if len(scales) > 1:
+            draws.append(int(rng.randint(len(scales))))
+            return draws[-1], tuple(scales[draws[-1]])
+        return 0, tuple(scales[0])                                           # mmdet's Resize draws nothing for one scale
+
+    if policy == 0:
+        i, scale = pick(img_scales)
+        oh, ow = rescale_size(h, w, scale)
+        return dict(policy=0, scale_idx=i, scale=scale, plan=(0, 0, 0, 0, 0, 0, oh, ow), draws=draws, crop=None,
+                    pano_ratio_v=[0.0, 1.0], pano_lr_noadj=None)
+    fi, fscale = pick(cfg["first_scales"])
+    h1, w1 = rescale_size(h, w, fscale)
+    crop_h = int(rng.randint(min(h1, lo), min(h1, hi) + 1))
+    crop_w = int(rng.randint(min(h1, lo), min(h1, hi) + 1))                  # the height's range: the reference's quirk
+    offset_h = int(rng.randint(0, max(h1 - crop_h, 0) + 1))
+    offset_w = int(rng.randint(0, max(w1 - crop_w, 0) + 1))
+    draws += [crop_h, crop_w, offset_h, offset_w]
+    i, scale = pick(img_scales)
+    ch, cw = min(crop_h, h1 - offset_h), min(crop_w, w1 - offset_w)
+    oh, ow = rescale_size(ch, cw, scale)
+    return dict(policy=1, scale_idx=i, scale=scale, plan=(h1, w1, offset_h, offset_w, ch, cw, oh, ow), draws=draws,
+                first_idx=fi, first_scale=fscale, h1=h1, w1=w1, crop_h=crop_h, crop_w=crop_w, offset_h=offset_h,
+                offset_w=offset_w, ch=ch, cw=cw, crop=(offset_h, offset_w, offset_h + ch, offset_w + cw),
+                pano_ratio_v=[offset_h / h1, (offset_h + crop_h) / h1], pano_lr_noadj=cw == w1)
 
 
 def make_pano_params(stretch, kx, ky, roll_dist, flip, W):
@@ -216,6 +272,69 @@ def resize_normalize_pad(imgs_u8, out_hw, mean=IMG_NORM_MEAN, std=IMG_NORM_STD, 
     return out
 
 
+def _host_plan(plan, B, what):
+    """Host plan (one dict of PLAN_KEYS or one 8-tuple per image) -> validated list of 8-tuples."""
+    rows = []
+    for p in plan:
+        try:
+            rows.append(tuple(int(p[k]) for k in PLAN_KEYS) if isinstance(p, dict) else tuple(int(v) for v in p))
+        except (KeyError, TypeError, ValueError) as e:
+            raise PswinError(f"{what}: a plan row is a dict of {PLAN_KEYS} or a tuple of those 8 integers; got {p!r}") from e
+    if len(rows) != B or any(len(r) != 8 for r in rows):
+        raise PswinError(f"{what}: need {B} plan rows of 8 integers, got {rows}")
+    for h1, w1, cy, cx, ch, cw, oh, ow in rows:
+        if oh < 1 or ow < 1:
+            raise PswinError(f"{what}: the output size must be positive, got {(oh, ow)}")
+        if h1 == 0:
+            continue
+        if h1 < 0 or w1 < 1 or ch < 1 or cw < 1:
+            raise PswinError(f"{what}: the intermediate size and the crop size must be positive, got {(h1, w1)} and {(ch, cw)}")
+        if cy < 0 or cx < 0 or cy + ch > h1 or cx + cw > w1:
+            raise PswinError(f"{what}: the crop {ch}x{cw} at ({cy}, {cx}) leaves the intermediate image {h1}x{w1}")
+    return rows
+
+
+def resize_crop_resize_normalize_pad(imgs_u8, plan, mean=IMG_NORM_MEAN, std=IMG_NORM_STD, to_rgb=True, size_divisor=32, pad_hw=None,
+                                     out=None, norm=None):
+    """resize_normalize_pad with a per-image plan in place of out_hw: (h1, w1, cy, cx, ch, cw, oh, ow).  h1 == 0 resizes the image to
+    oh x ow; h1 > 0 resizes it to h1 x w1 (uint8), crops [cy:cy+ch, cx:cx+cw] and resizes the crop to oh x ow -- in one launch, the
+    intermediate image is never stored.  plan: host list of dicts (PLAN_KEYS) or 8-tuples, validated here, or a device int32 [B, 8]
+    tensor, clamped on the device (then pad_hw must be given).  The other arguments: as resize_normalize_pad."""
+    what = "resize_crop_resize_normalize_pad"
+    _check_images(imgs_u8, what, (3,))
+    B, H, W, _ = imgs_u8.shape
+    dev = imgs_u8.device
+    if isinstance(plan, torch.Tensor):
+        if pad_hw is None:
+            raise PswinError(f"{what}: pass pad_hw with a device plan tensor")
+        if plan.dtype != torch.int32 or tuple(plan.shape) != (B, 8) or plan.device != dev or not plan.is_contiguous():
+            raise PswinError(f"{what}: plan must be a contiguous int32 [B, 8] tensor on the images' device")
+        plan_t = plan
+    else:
+        rows = _host_plan(plan, B, what)
+        sizes = [(r[6], r[7]) for r in rows]
+        if pad_hw is None:
+            pad_hw = padded_size(sizes, size_divisor)
+        if any(h > pad_hw[0] or w > pad_hw[1] for h, w in sizes):
+            raise PswinError(f"{what}: an output size exceeds the padded size {tuple(pad_hw)}")
+        plan_t = torch.tensor(rows, dtype=torch.int32, device=dev)
+    Hp, Wp = int(pad_hw[0]), int(pad_hw[1])
+    if Hp < 1 or Wp < 1:
+        raise PswinError(f"{what}: the padded size must be positive, got {pad_hw}")
+    if norm is None:
+        norm = norm_tensor(mean, std, dev)
+    else:
+        _check_buffer(norm, what, "norm", torch.float32, (6,), dev)
+    x = imgs_u8.contiguous()
+    if out is None:
+        out = torch.empty(B, 3, Hp, Wp, device=dev, dtype=torch.float32)
+    else:
+        _check_buffer(out, what, "out", torch.float32, (B, 3, Hp, Wp), dev, (x, plan_t, norm))
+    _lib.call("pswin_pano_resize_crop_resize_normalize_pad", x, _lib.ptr(x), _lib.ptr(plan_t), _lib.ptr(norm), int(bool(to_rgb)),
+              _lib.ptr(out), B, H, W, Hp, Wp, algo_bytes=x.numel() + out.numel() * 4)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # boxes (host, numpy)
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -317,6 +436,28 @@ def resize_boxes(boxes, h, w, new_h, new_w):
     return b
 
 
+def crop_boxes(boxes, labels, offset_w, offset_h, crop_h, crop_w):
+    """mmdet RandomCrop._crop_data on the boxes (transforms.py:881-900): subtract the offset in float32, clip to the crop, keep the
+    boxes with x2 > x1 and y2 > y1 and their labels.  crop_h, crop_w: the crop as taken.  An empty result is valid."""
+    b = np.asarray(boxes, np.float32).reshape(-1, 4) - np.array([offset_w, offset_h, offset_w, offset_h], dtype=np.float32)
+    labels = np.asarray(labels, np.int64).reshape(-1)
+    if len(b) != len(labels):
+        raise PswinError(f"crop_boxes: {len(b)} boxes but {len(labels)} labels")
+    b[:, 0::2] = np.clip(b[:, 0::2], 0, crop_w)
+    b[:, 1::2] = np.clip(b[:, 1::2], 0, crop_h)
+    keep = (b[:, 2] > b[:, 0]) & (b[:, 3] > b[:, 1])
+    return b[keep, :], labels[keep]
+
+
+def auto_augment_boxes(boxes, labels, h, w, aa):
+    """One image's boxes and labels through the policy that draw_auto_augment returned for its h x w image."""
+    h1, w1, cy, cx, ch, cw, oh, ow = aa["plan"]
+    if aa["policy"] == 0:
+        return resize_boxes(boxes, h, w, oh, ow), np.asarray(labels, np.int64).reshape(-1)
+    b, l = crop_boxes(resize_boxes(boxes, h, w, h1, w1), labels, cx, cy, ch, cw)
+    return resize_boxes(b, ch, cw, oh, ow), l
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # the recipe
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -327,13 +468,20 @@ class PanoTrainTransform:
         x, boxes, labels, img_metas = PanoTrainTransform()(imgs_u8, boxes, labels)
 
     imgs_u8: uint8 [B, H, W, 3] BGR on the device, all of one size (group mixed sizes into separate calls); boxes: list of float32
-    [n_i, 4]; labels: list of int64 [n_i].  x: float32 [B, 3, Hp, Wp], the backbone's input."""
+    [n_i, 4]; labels: list of int64 [n_i].  x: float32 [B, 3, Hp, Wp], the backbone's input.
+
+    auto_augment=STREETWIN_AUTO_AUGMENT puts the recipe's AutoAugment in the place of the Resize: per image either the Resize or
+    Resize -> RandomCrop -> Resize (module docstring), both policies of a batch in one launch.  img_metas then also hold
+    auto_augment_policy, crop ((y1, x1, y2, x2) in the first resize's image, or None), pano_ratio_v and pano_lr_noadj (crop width ==
+    w1; None without a crop, where the reference leaves the key out); img_shape, scale, scale_factor (new / crop) and pad_shape
+    describe the final resize, as mmdet leaves them."""
 
     def __init__(self, kxy=(2.0, 2.0), stretch_chance=1.0, roll_chance=1.0, clip01=True, flip_ratio=0.5, img_scales=TRAIN_RESIZE_SCALES,
-                 mean=IMG_NORM_MEAN, std=IMG_NORM_STD, to_rgb=True, size_divisor=32, rng=np.random):
+                 mean=IMG_NORM_MEAN, std=IMG_NORM_STD, to_rgb=True, size_divisor=32, rng=np.random, auto_augment=None):
         self.kxy, self.stretch_chance, self.roll_chance, self.clip01 = tuple(kxy), stretch_chance, roll_chance, clip01
         self.flip_ratio, self.img_scales = flip_ratio, [tuple(s) for s in img_scales]
         self.mean, self.std, self.to_rgb, self.size_divisor, self.rng = mean, std, to_rgb, size_divisor, rng
+        self.auto_augment = auto_augment
         self._norm = {}
 
     def draw(self, B, W):
@@ -345,11 +493,53 @@ class PanoTrainTransform:
         params = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
         return params, scales
 
+    def draw_auto(self, B, H, W):
+        """Per image: the pano parameters, then the AutoAugment draws (the reference's order)."""
+        parts, aas = [], []
+        for _ in range(B):
+            parts.append(draw_pano_params(1, W, self.kxy, self.stretch_chance, self.roll_chance, self.flip_ratio, self.rng))
+            aas.append(draw_auto_augment(H, W, self.auto_augment, self.rng, self.img_scales))
+        return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}, aas
+
+    def _call_auto(self, imgs_u8, boxes, labels):
+        B, H, W, _ = imgs_u8.shape
+        params, aas = self.draw_auto(B, H, W)
+        plan = [a["plan"] for a in aas]
+        pad_hw = padded_size([p[6:] for p in plan], self.size_divisor)
+        dev = imgs_u8.device
+        if dev not in self._norm:
+            self._norm[dev] = norm_tensor(self.mean, self.std, dev)
+        x = resize_crop_resize_normalize_pad(pano_warp(imgs_u8, params), plan, to_rgb=self.to_rgb, size_divisor=self.size_divisor,
+                                             pad_hw=pad_hw, norm=self._norm[dev])
+        boxes, labels = transform_boxes(boxes, labels, H, W, params, self.clip01)
+        metas = []
+        d = self.size_divisor or 1
+        for i, a in enumerate(aas):
+            h1, w1, cy, cx, ch, cw, nh, nw = a["plan"]
+            boxes[i], labels[i] = auto_augment_boxes(boxes[i], labels[i], H, W, a)
+            fh, fw = (ch, cw) if a["policy"] else (H, W)                   # what the final resize took in
+            m = self._meta(params, i, H, W, nh, nw, fh, fw, a["scale"], pad_hw, d)
+            m.update(auto_augment_policy=a["policy"], crop=a["crop"], pano_ratio_v=a["pano_ratio_v"], pano_lr_noadj=a["pano_lr_noadj"])
+            metas.append(m)
+        return x, boxes, labels, metas
+
+    def _meta(self, params, i, H, W, nh, nw, fh, fw, scale, pad_hw, d):
+        return dict(ori_shape=(H, W, 3), img_shape=(nh, nw, 3), pad_shape=(-(-nh // d) * d, -(-nw // d) * d, 3),
+                    batch_input_shape=tuple(pad_hw), scale=scale,
+                    scale_factor=np.array([nw / fw, nh / fh, nw / fw, nh / fh], np.float32),
+                    flip=bool(params["flip"][i]), flip_direction="horizontal" if params["flip"][i] else None,
+                    pano_stretch=(float(params["kx"][i]), float(params["ky"][i])) if params["stretch"][i] else None,
+                    roll_dist=float(params["roll_dist"][i]) if params["roll"][i] else None, roll_shift=int(params["shift"][i]),
+                    img_norm_cfg=dict(mean=np.array(self.mean, np.float32), std=np.array(self.std, np.float32),
+                                      to_rgb=self.to_rgb))
+
     def __call__(self, imgs_u8, boxes, labels):
         _check_images(imgs_u8, "PanoTrainTransform", (3,))
         B, H, W, _ = imgs_u8.shape
         if len(boxes) != B or len(labels) != B:
             raise PswinError(f"PanoTrainTransform: {B} images but {len(boxes)} box arrays and {len(labels)} label arrays")
+        if self.auto_augment is not None:
+            return self._call_auto(imgs_u8, boxes, labels)
         params, scales = self.draw(B, W)
         sizes = [rescale_size(H, W, s) for s in scales]
         pad_hw = padded_size(sizes, self.size_divisor)
@@ -362,13 +552,5 @@ class PanoTrainTransform:
         metas = []
         for i, (nh, nw) in enumerate(sizes):
             boxes[i] = resize_boxes(boxes[i], H, W, nh, nw)
-            d = self.size_divisor or 1
-            metas.append(dict(ori_shape=(H, W, 3), img_shape=(nh, nw, 3), pad_shape=(-(-nh // d) * d, -(-nw // d) * d, 3),
-                              batch_input_shape=tuple(pad_hw), scale=scales[i],
-                              scale_factor=np.array([nw / W, nh / H, nw / W, nh / H], np.float32),
-                              flip=bool(params["flip"][i]), flip_direction="horizontal" if params["flip"][i] else None,
-                              pano_stretch=(float(params["kx"][i]), float(params["ky"][i])) if params["stretch"][i] else None,
-                              roll_dist=float(params["roll_dist"][i]) if params["roll"][i] else None, roll_shift=int(params["shift"][i]),
-                              img_norm_cfg=dict(mean=np.array(self.mean, np.float32), std=np.array(self.std, np.float32),
-                                                to_rgb=self.to_rgb)))
+            metas.append(self._meta(params, i, H, W, nh, nw, H, W, scales[i], pad_hw, self.size_divisor or 1))
         return x, boxes, labels, metas
