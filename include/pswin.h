@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSWIN_ABI_VERSION 3
+#define PSWIN_ABI_VERSION 4
 
 #define PSWIN_F32 0
 #define PSWIN_BF16 1
@@ -493,6 +493,28 @@ int pswin_roi_align_bwd(const pswin_roi_levels* levels, const float* rois, const
 int pswin_nms_workspace(int groups, int nmax);                 /* bytes of workspace for pswin_nms_groups (the suppression bit masks); groups <= 2048 */
 int pswin_nms_groups(const float* boxes, const int32_t* counts, int groups, int nmax, float iou_threshold, unsigned char* keep, void* workspace,
                      void* stream);
+
+/* MaxIoUAssigner.assign for a padded batch (mmdet/core/bbox/assigners/max_iou_assigner.py:85-212; gt_max_assign_all = True, no
+ * gt_bboxes_ignore): the target assignment of the RPN and of the RoI head, with the per-image box count read from DEVICE memory, so that
+ * a captured step takes the next batch's annotations by copying them into the same buffers.
+ *   cand      f32 [N][4] shared by every image (cand_per_image = 0: the RPN's anchors) or [B][N][4] (cand_per_image = 1: the RoI stage)
+ *   gt        f32 [B][Gmax][4], gt_count int32 [B] on the device: rows at index >= gt_count[b] are padding and are never read as boxes
+ *   lead_gt   0, or the number of leading candidates of image b that are its own gt rows (add_gt_as_proposals: Gmax); a candidate
+ *             i < lead_gt with i >= gt_count[b] is padding: gt_inds = -1, max_iou = -1, and it takes no part in any maximum
+ *   gt_inds   int64 [B][N]: -1 ignore, 0 negative, g + 1 matched to gt g;  max_iou f32 [B][N] or NULL
+ * For image b with G = gt_count[b]: G == 0 -> every other candidate gets gt_inds = 0 and max_iou = 0 (:147-153); otherwise IoU as
+ * detector.box_iou (clamped widths, union (area_gt + area_cand) - inter floored at 1e-6), best = max over g, arg = the lowest g that
+ * reaches it; 0 <= best < neg_iou_thr -> 0; best >= pos_iou_thr -> arg + 1; with match_low_quality every candidate whose IoU with gt g
+ * EQUALS that gt's maximum over the valid candidates is reassigned to g + 1 when that maximum is >= min_pos_iou (the largest such g: the
+ * reference's sequential loop).  Inputs are finite; the result with a NaN is unspecified.
+ * Two launches, no atomics, nothing to clear between calls: per-workgroup partial maxima go to `workspace` with plain stores and are
+ * folded in index order, so the outputs are bit-identical from call to call and from graph replay to graph replay.
+ * 1 <= Gmax <= 256, N >= 1, B >= 1, 0 <= lead_gt <= N, 16-byte aligned cand / gt / workspace; anything else is PSWIN_ERR_ARG. */
+int pswin_max_iou_assign_rows_per_workgroup(void);              /* candidates one workgroup of the first launch covers */
+int pswin_max_iou_assign_workspace(int B, int N, int Gmax);     /* bytes of workspace for pswin_max_iou_assign, or PSWIN_ERR_ARG */
+int pswin_max_iou_assign(const float* cand, int cand_per_image, const float* gt, const int32_t* gt_count, int B, int N, int Gmax, int lead_gt,
+                         float pos_iou_thr, float neg_iou_thr, float min_pos_iou, int match_low_quality, long long* gt_inds, float* max_iou,
+                         void* workspace, void* stream);
 
 int pswin_gemm_nt_supported(long long M, int K, int N);
 int pswin_gemm_nt(const void* x, const void* w, const float* bias, void* y, long long M, int K, int N, int tile_m, void* stream);

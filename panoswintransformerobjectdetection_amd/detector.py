@@ -16,6 +16,11 @@ so nothing here is checked against reference outputs.  RoIAlign is the published
 (adaptive grid) as hand-written HIP kernels, forward and backward (csrc/pswin_roi.hip, checked against a plain PyTorch statement
 of the definition in tests/); NMS is the greedy rule: on the GPU one HIP launch per image (nms_keep_groups -> pswin_nms_groups), on the CPU a fixed-point iteration (nms_keep).  The other
 head operators are ordinary PyTorch-ROCm operators (MIOpen / hipBLASLt, bf16 autocast).
+
+TARGETS: a list of dicts per image (shapes tied to one batch), or a PaddedTargets (fixed shapes, the box count of every image on the
+device: the form a captured step is replayed on with the next batch's annotations).  With a PaddedTargets both stages' MaxIoUAssigner
+run as HIP kernels for the whole batch (max_iou_assign_batch -> pswin_max_iou_assign), pinned to the reference's own results
+(tests/golden/max_iou_assign_batch.npz).
 """
 import math
 
@@ -142,6 +147,91 @@ def nms_keep_groups(box_list, iou_thr):
         from . import ops
         return ops.nms_groups(box_list, iou_thr)
     return [nms_keep(b, iou_thr) for b in box_list]
+
+
+def max_iou_assign_batch(cand, gt, gt_count, pos, neg, min_pos, match_low_quality, lead_gt=0):
+    """max_iou_assign for a padded batch: (gt_inds long [B, N], max_iou f32 [B, N]).  cand [N, 4] (shared by the images) or [B, N, 4];
+    gt [B, Gmax, 4] of which the first gt_count[b] (int32 [B]) rows of image b are boxes.  With lead_gt > 0 the first lead_gt candidates
+    of an image are its own padded gt rows (add_gt_as_proposals): those past the count are padding, come back as gt_inds = -1 /
+    max_iou = -1 and take part in no maximum.  An image without boxes: every other candidate 0 / 0 (max_iou_assigner.py:147-153).
+    On the GPU: two HIP launches for the whole batch that read the counts from the device (ops.max_iou_assign_batch ->
+    pswin_max_iou_assign), so a captured step follows the buffers; on the CPU (the definition): image by image through
+    max_iou_assign on the valid rows."""
+    if gt.is_cuda:
+        from . import ops
+        return ops.max_iou_assign_batch(cand, gt, gt_count, pos, neg, min_pos, match_low_quality, lead_gt)
+    B, N = gt.shape[0], cand.shape[-2]
+    inds = torch.full((B, N), -1, dtype=torch.long)
+    best = torch.full((B, N), -1.0)
+    for b, G in enumerate(gt_count.tolist()):
+        c = cand[b] if cand.dim() == 3 else cand
+        valid = torch.ones(N, dtype=torch.bool)
+        valid[G:lead_gt] = False
+        if G == 0:
+            inds[b, valid], best[b, valid] = 0, 0.0
+            continue
+        inds[b, valid] = max_iou_assign(c[valid], gt[b, :G], pos, neg, min_pos, match_low_quality)
+        best[b, valid] = box_iou(gt[b, :G], c[valid]).max(0)[0]
+    return inds, best
+
+
+class PaddedTargets:
+    """The annotations of a batch in buffers of a fixed shape, for a captured detector step: boxes f32 [B, Gmax, 4], labels int64
+    [B, Gmax], count int32 [B] (the first count[b] rows of image b are boxes, the rest zeros) and masks uint8 [B, Gmax, H, W] or None
+    (Faster R-CNN).  The captured step reads the buffers; `copy_from` puts the next batch into them, outside the capture and on the
+    stream the step is replayed on."""
+
+    def __init__(self, boxes, labels, count, masks=None):
+        self.boxes, self.labels, self.count, self.masks = boxes, labels, count, masks
+
+    @classmethod
+    def allocate(cls, B, max_gt, device, mask_hw=None):
+        masks = None if mask_hw is None else torch.zeros(B, max_gt, int(mask_hw[0]), int(mask_hw[1]), dtype=torch.uint8, device=device)
+        return cls(torch.zeros(B, max_gt, 4, device=device), torch.zeros(B, max_gt, dtype=torch.long, device=device),
+                   torch.zeros(B, dtype=torch.int32, device=device), masks)
+
+    @property
+    def max_gt(self):
+        return self.boxes.shape[1]
+
+    def copy_from(self, boxes, labels, masks=None):
+        """boxes / labels (/ masks): one [G, 4] / [G] (/ [G, H, W]) numpy array or tensor per image (what PanoTrainTransform returns).
+        Pads with zeros and copies into the existing buffers in place."""
+        from ._lib import PswinError
+        B, Gmax = self.boxes.shape[:2]
+        if len(boxes) != B or len(labels) != B or (masks is not None and len(masks) != B):
+            raise PswinError(f"PaddedTargets.copy_from: the buffers hold {B} images, got {len(boxes)} box and {len(labels)} label arrays")
+        if (masks is None) != (self.masks is None):
+            raise PswinError("PaddedTargets.copy_from: masks must be given exactly when the buffers were allocated with mask_hw")
+        bx, lb = [torch.as_tensor(v).detach().to("cpu", torch.float32).reshape(-1, 4) for v in boxes], \
+                 [torch.as_tensor(v).detach().to("cpu", torch.long).reshape(-1) for v in labels]
+        counts = [v.shape[0] for v in bx]
+        if max(counts) > Gmax:
+            raise PswinError(f"PaddedTargets.copy_from: an image has {max(counts)} boxes, the buffers hold max_gt = {Gmax}")
+        if any(l.shape[0] != n for l, n in zip(lb, counts)) or (masks is not None and any(len(m) != n for m, n in zip(masks, counts))):
+            raise PswinError("PaddedTargets.copy_from: one label (and one mask) per box")
+        hb, hl = torch.zeros(B, Gmax, 4), torch.zeros(B, Gmax, dtype=torch.long)
+        for b, n in enumerate(counts):
+            hb[b, :n], hl[b, :n] = bx[b], lb[b]
+        self.boxes.copy_(hb)
+        self.labels.copy_(hl)
+        self.count.copy_(torch.tensor(counts, dtype=torch.int32))
+        if masks is not None:
+            self.masks.zero_()
+            for b, n in enumerate(counts):
+                if n:
+                    self.masks[b, :n].copy_(torch.as_tensor(masks[b]).to(torch.uint8))
+        return self
+
+    def as_lists(self):
+        """The list-of-dicts form of the same annotations (reads the counts back: not for a captured step)."""
+        out = []
+        for b, n in enumerate(self.count.tolist()):
+            d = {"boxes": self.boxes[b, :n], "labels": self.labels[b, :n]}
+            if self.masks is not None:
+                d["masks"] = self.masks[b, :n]
+            out.append(d)
+        return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -282,6 +372,7 @@ class MiniMaskRCNN(nn.Module):
     STRIDES = (4, 8, 16, 32, 64)
     rand_like = staticmethod(torch.rand_like)    # the samplers' random keys (tests substitute a fixed sequence to compare eager and replayed steps)
     roi_align = staticmethod(roi_align)          # the HIP operator; tests of the head stand-ins on the CPU substitute the PyTorch statement
+    assign = staticmethod(max_iou_assign_batch)  # the target assigner of a PaddedTargets batch (both stages, once per batch each)
 
     def __init__(self, backbone_cfg, num_classes=80):
         super().__init__()
@@ -321,18 +412,25 @@ class MiniMaskRCNN(nn.Module):
         loss_cls = loss_reg = cls_all.new_zeros(())
         n_pos_max, n_tot = int(cfg["num"] * cfg["pos_fraction"]), cfg["num"]
         proposals = []
+        padded = isinstance(targets, PaddedTargets)
+        if padded:                                                                                # the anchors are shared by the images
+            inds_all = self.assign(flat_a, targets.boxes, targets.count, cfg["pos"], cfg["neg"], cfg["min_pos"], True)[0]
         for b in range(B):
-            gt = targets[b]["boxes"]
             # MaxIoUAssigner(pos 0.7, neg 0.3, min_pos 0.3, match_low_quality) -- configs/_base_/models/mask_rcnn_swin_fpn.py:79-85
-            gt_inds = max_iou_assign(flat_a, gt, cfg["pos"], cfg["neg"], cfg["min_pos"], True)
+            if padded:
+                gt, gt_inds = targets.boxes[b], inds_all[b]                                       # [Gmax, 4]: rows past the count are never matched
+            else:
+                gt = targets[b]["boxes"]
+                gt_inds = max_iou_assign(flat_a, gt, cfg["pos"], cfg["neg"], cfg["min_pos"], True)
             label = gt_inds.clamp(max=1).to(flat_a.dtype)                                         # 1 positive, 0 negative, -1 neither
             arg = (gt_inds - 1).clamp(min=0)
             best = label
             # random sampling with static shapes: rank by a random key, positives first
             key = self.rand_like(best)
-            pos_rank = torch.argsort(torch.where(label == 1, key, key + 2))[:n_pos_max]
+            behind = torch.where(label < 0, key + 4, key + 2) if padded else key + 2              # padded: ignored behind everything
+            pos_rank = torch.argsort(torch.where(label == 1, key, behind))[:n_pos_max]
             pos_valid = label[pos_rank] == 1
-            neg_rank = torch.argsort(torch.where(label == 0, key, key + 2))[:n_tot]
+            neg_rank = torch.argsort(torch.where(label == 0, key, behind))[:n_tot]
             n_pos = pos_valid.sum()
             neg_valid = (label[neg_rank] == 0) & (torch.arange(n_tot, device=key.device) < (n_tot - n_pos))
             idx = torch.cat([pos_rank, neg_rank])
@@ -365,21 +463,33 @@ class MiniMaskRCNN(nn.Module):
         cfg = self.rcnn_cfg
         n_tot, n_pos_max = cfg["num"], int(cfg["num"] * cfg["pos_fraction"])
         rois, labels, reg_t, pos_valid_all, gt_idx_all = [], [], [], [], []
+        padded = isinstance(targets, PaddedTargets)
         with torch.no_grad():
+            if padded:                                                                            # add_gt_as_proposals: the padded gt rows lead
+                cand_all = torch.cat([targets.boxes, torch.stack(proposals)], 1)
+                inds_all = self.assign(cand_all, targets.boxes, targets.count, cfg["pos"], cfg["pos"], cfg["pos"], True,
+                                       lead_gt=targets.max_gt)[0]
             for b, props in enumerate(proposals):
-                gt, gl = targets[b]["boxes"], targets[b]["labels"]
-                cand = torch.cat([gt, props], 0)                                                  # add_gt_as_proposals
                 # MaxIoUAssigner(pos 0.5, neg 0.5, min_pos 0.5, match_low_quality=True) -- mask_rcnn_swin_fpn.py:101-107
-                gt_inds = max_iou_assign(cand, gt, cfg["pos"], cfg["pos"], cfg["pos"], True)
+                if padded:
+                    gt, gl, cand, gt_inds = targets.boxes[b], targets.labels[b], cand_all[b], inds_all[b]
+                else:
+                    gt, gl = targets[b]["boxes"], targets[b]["labels"]
+                    cand = torch.cat([gt, props], 0)                                              # add_gt_as_proposals
+                    gt_inds = max_iou_assign(cand, gt, cfg["pos"], cfg["pos"], cfg["pos"], True)
                 is_pos, arg = gt_inds > 0, (gt_inds - 1).clamp(min=0)
                 best = is_pos.float()
                 key = self.rand_like(best)
-                pos_rank = torch.argsort(torch.where(is_pos, key, key + 2))[:n_pos_max]
+                # padded: the negatives are gt_inds == 0, and the ignored rows (the gt padding) sort behind everything in both orders,
+                # so that a padding row is never drawn as a RoI or as a background filler
+                is_neg = gt_inds == 0 if padded else ~is_pos
+                behind = torch.where(gt_inds < 0, key + 4, key + 2) if padded else key + 2
+                pos_rank = torch.argsort(torch.where(is_pos, key, behind))[:n_pos_max]
                 pos_valid = is_pos[pos_rank]
                 # the positive slots that found no positive were filled with the lowest-key non-positives (they count as background
                 # below): the negatives proper are the NEXT ones in that order, so that no RoI is sampled twice
                 filler = n_pos_max - pos_valid.sum()
-                neg_order = torch.argsort(torch.where(~is_pos, key, key + 2))
+                neg_order = torch.argsort(torch.where(is_neg, key, behind))
                 take = (torch.arange(n_tot - n_pos_max, device=key.device) + filler).clamp(max=neg_order.numel() - 1)
                 neg_rank = neg_order[take]
                 idx = torch.cat([pos_rank, neg_rank])
@@ -401,6 +511,8 @@ class MiniMaskRCNN(nn.Module):
         ar = torch.arange(pos_sel.numel(), device=reg.device)
         reg_p = reg.float()[pos_sel].view(-1, self.num_classes, 4)[ar, pl]
         loss_bbox = ((reg_p - torch.cat(reg_t)).abs().sum(1) * pv).sum() / (B * n_tot)
+        if padded and targets.masks is None:                                                      # Faster R-CNN: no mask branch
+            return loss_cls, loss_bbox, None
         # masks on the positive RoIs (the first n_pos_max of every image)
         xm = self.roi_align(feats[:4], self.STRIDES[:4], rois_b[:, :n_pos_max], 14)
         logits = self.mask_head(xm.to(feats[0].dtype)).float()                                    # [B * P, classes, 28, 28]
@@ -415,7 +527,7 @@ class MiniMaskRCNN(nn.Module):
                 gx = (r[:, 0:1] + (r[:, 2:3] - r[:, 0:1]) * t[None]) / W * 2 - 1
                 gy = (r[:, 1:2] + (r[:, 3:4] - r[:, 1:2]) * t[None]) / H * 2 - 1
                 grid = torch.stack([gx[:, None, :].expand(-1, ms, ms), gy[:, :, None].expand(-1, ms, ms)], -1).reshape(1, -1, ms, 2)
-                gm = targets[b]["masks"].float()[None]                                            # [1, G, H, W]: all gt bitmaps as channels
+                gm = (targets.masks[b] if padded else targets[b]["masks"]).float()[None]          # [1, G, H, W]: all gt bitmaps as channels
                 smp = F.grid_sample(gm, grid, mode="bilinear", padding_mode="zeros", align_corners=False)   # [1, G, P * ms, ms]
                 smp = smp[0].view(gm.shape[1], n_pos_max, ms, ms)
                 mt.append((smp[gt_idx_all[b], torch.arange(n_pos_max, device=smp.device)] >= 0.5).float())
@@ -425,7 +537,9 @@ class MiniMaskRCNN(nn.Module):
         return loss_cls, loss_bbox, loss_mask
 
     def heads_loss(self, feats, targets, img_hw):
-        """Everything behind the backbone: dict of the 5 Mask R-CNN losses (two_stage.py:116-175)."""
+        """Everything behind the backbone: dict of the 5 Mask R-CNN losses (two_stage.py:116-175).  targets: a list of dicts (boxes,
+        labels, masks) per image, or a PaddedTargets -- fixed shapes whatever the images' box counts, the form a captured step can be
+        replayed on; without masks it is the Faster R-CNN step (4 losses)."""
         if self.channels_last:
             feats = [f.contiguous(memory_format=torch.channels_last) for f in feats]
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):
@@ -435,7 +549,10 @@ class MiniMaskRCNN(nn.Module):
         l_rpn_cls, l_rpn_reg, proposals = self._rpn_losses_and_proposals(rpn_outs, anchors, targets, img_hw)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):
             l_cls, l_bbox, l_mask = self._roi_losses(fpn, proposals, targets, img_hw)
-        return {"loss_rpn_cls": l_rpn_cls, "loss_rpn_bbox": l_rpn_reg, "loss_cls": l_cls, "loss_bbox": l_bbox, "loss_mask": l_mask}
+        losses = {"loss_rpn_cls": l_rpn_cls, "loss_rpn_bbox": l_rpn_reg, "loss_cls": l_cls, "loss_bbox": l_bbox}
+        if l_mask is not None:
+            losses["loss_mask"] = l_mask
+        return losses
 
     def forward_train(self, img, targets):
         return self.heads_loss(self.backbone(img), targets, img.shape[2:])

@@ -1550,6 +1550,32 @@ def nms_groups(box_list, iou_thr):
     return [keep[g, :ns[g]].bool() for g in range(len(ns))]
 
 
+def max_iou_assign_batch(cand, gt, gt_count, pos_iou_thr, neg_iou_thr, min_pos_iou=0.0, match_low_quality=True, lead_gt=0, want_max_iou=True):
+    """MaxIoUAssigner.assign for a padded batch in TWO launches (pswin_max_iou_assign): (gt_inds int64 [B, N], max_iou f32 [B, N] or None).
+    cand: f32 [N, 4] shared by the images or [B, N, 4]; gt: f32 [B, Gmax, 4]; gt_count: int32 [B] ON THE DEVICE (rows past it are padding);
+    lead_gt: the number of leading candidates that are the image's own gt rows (those past the count come back as -1).  No host-to-device
+    copy and no host synchronisation: the call can be captured, and a replay reads whatever boxes and counts the buffers hold then.  The
+    partial maxima live in one workspace per (B, N, Gmax, device), written in full by every call before it is read."""
+    if gt.dim() != 3 or gt.shape[2] != 4 or cand.dim() not in (2, 3) or cand.shape[-1] != 4 or (cand.dim() == 3 and cand.shape[0] != gt.shape[0]):
+        raise PswinError(f"max_iou_assign_batch: candidates [N, 4] or [B, N, 4] and gt [B, Gmax, 4], got {tuple(cand.shape)} and {tuple(gt.shape)}")
+    B, Gmax = int(gt.shape[0]), int(gt.shape[1])
+    N = int(cand.shape[-2])
+    if gt_count.dtype != torch.int32 or tuple(gt_count.shape) != (B,) or gt_count.device != gt.device or cand.device != gt.device:
+        raise PswinError("max_iou_assign_batch: gt_count must be an int32 [B] tensor on the device of the boxes")
+    cand, gt, gt_count = cand.detach().float().contiguous(), gt.detach().float().contiguous(), gt_count.contiguous()
+    nbytes = int(_lib.load().pswin_max_iou_assign_workspace(B, N, Gmax))
+    _lib.check(min(nbytes, 0), "pswin_max_iou_assign_workspace")
+    key = ("assign_ws", B, N, Gmax, _dev_key(gt.device))
+    if key not in _CACHE:
+        _CACHE[key] = torch.empty(nbytes, dtype=torch.uint8, device=gt.device)
+    inds = torch.empty(B, N, dtype=torch.int64, device=gt.device)
+    miou = torch.empty(B, N, dtype=torch.float32, device=gt.device) if want_max_iou else None
+    call("pswin_max_iou_assign", gt, ptr(cand), int(cand.dim() == 3), ptr(gt), ptr(gt_count), B, N, Gmax, int(lead_gt),
+         ctypes.c_float(float(pos_iou_thr)), ctypes.c_float(float(neg_iou_thr)), ctypes.c_float(float(min_pos_iou)), int(bool(match_low_quality)),
+         ptr(inds), ptr(miou), ptr(_CACHE[key]))
+    return inds, miou
+
+
 # ------------------------------------------------------------------------------------------------
 # qkv Linear + attention core in one kernel for C = 192 / 384 (pswin_qkv_attn_fused_fwd, round 3)
 # ------------------------------------------------------------------------------------------------
