@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PSWIN_LIB") or os.path.join(_PKG, "libpswin_hip.so") 
 F32, BF16 = 0, 1
 MODE_PLANAR, MODE_PANO = 0, 1
 WS, WTOK, WPAD, HEAD_DIM = 7, 49, 64, 32
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -83,6 +83,12 @@ _PROTOTYPES = {
     "pswin_max_iou_assign_rows_per_workgroup": [],
     "pswin_max_iou_assign_workspace": [_i, _i, _i],
     "pswin_max_iou_assign": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp],
+    "pswin_multiclass_nms_scores": [_vp, _i, _vp, _i, _i, _i, _f, _vp, _vp],
+    "pswin_multiclass_nms_workspace": [_i, _i, _i],
+    "pswin_multiclass_nms": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
+    "pswin_multiclass_nms_select": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pswin_paste_masks": [_vp, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i, _i, _i,
+                          _f, _vp, _vp],
     "pswin_gemm_nt_supported": [ctypes.c_longlong, _i, _i],
     "pswin_gemm_nt": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],
     "pswin_gemm_nt_f32": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],

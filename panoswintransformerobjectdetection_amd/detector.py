@@ -21,6 +21,12 @@ TARGETS: a list of dicts per image (shapes tied to one batch), or a PaddedTarget
 device: the form a captured step is replayed on with the next batch's annotations).  With a PaddedTargets both stages' MaxIoUAssigner
 run as HIP kernels for the whole batch (max_iou_assign_batch -> pswin_max_iou_assign), pinned to the reference's own results
 (tests/golden/max_iou_assign_batch.npz).
+
+INFERENCE: `heads_predict` / `simple_test` (TwoStageDetector.simple_test, mmdet/models/detectors/two_stage.py:217) return a Detections:
+fixed shapes, the detection count of every image on the device, no host synchronisation -- one captured graph serves every batch.  The
+definitions are multiclass_nms and paste_masks below (pure PyTorch; pinned to the reference where its tree allows:
+tests/golden/detect_post.npz); on the GPU both run as HIP kernels for the whole batch (ops.multiclass_nms_batch -> pswin_multiclass_nms,
+ops.paste_masks -> pswin_paste_masks).
 """
 import math
 
@@ -235,6 +241,145 @@ class PaddedTargets:
 
 
 # ------------------------------------------------------------------------------------------------------------------------
+# inference: class-wise NMS, mask paste, the fixed-shape result
+# ------------------------------------------------------------------------------------------------------------------------
+def decode_deltas_per_class(rois, deltas, stds, max_shape):
+    """decode_deltas for [R, 4 C] deltas, one box per class of every RoI (delta2bbox on the bbox head's output,
+    mmdet/core/bbox/coder/delta_xywh_bbox_coder.py:134-237): [R, 4 C]"""
+    R, C = deltas.shape[0], deltas.shape[1] // 4
+    src = rois[:, None, :].expand(R, C, 4).reshape(-1, 4)
+    return decode_deltas(src, deltas.reshape(-1, 4), stds, max_shape).reshape(R, 4 * C)
+
+
+def multiclass_nms(multi_bboxes, multi_scores, score_thr, iou_thr, max_num):
+    """Class-wise NMS of one image (multiclass_nms, mmdet/core/post_processing/bbox_nms.py:7-93, with mmcv's batched_nms: a box suppresses
+    only boxes of its own class).  multi_bboxes [R, 4 C], multi_scores [R, C + 1] with the background column last (ignored) ->
+    (dets [k, 5] = box and score, labels long [k], flat_index long [k] = r * C + c of each detection).
+
+    The candidates are the (r, c) with score > score_thr (strict).  Within a class the greedy rule runs in descending score: a candidate
+    is dropped when a kept candidate before it has box_iou > iou_thr with it.  The survivors of all classes are ordered by descending
+    score and cut to max_num (max_num <= 0: no cut).
+
+    TIES.  The reference leaves candidates of equal score to an unstable sort.  Here equal scores are ordered by ASCENDING flat index
+    r * C + c, inside the NMS (where, within a class, that is ascending r) and in the final order: the choice _topk_stable makes, for the
+    same reason -- a captured graph and its definition must agree on the bit."""
+    R, C = multi_scores.shape[0], multi_scores.shape[1] - 1
+    boxes, scores = multi_bboxes.reshape(R * C, 4), multi_scores[:, :C].reshape(-1)
+    cand = torch.nonzero(scores > score_thr)[:, 0]                     # ascending flat index
+    cand = cand[torch.sort(scores[cand], descending=True, stable=True)[1]]
+    labels = cand % C
+    keep = torch.ones(cand.numel(), dtype=torch.bool, device=cand.device)
+    for c in torch.unique(labels).tolist():
+        pos = torch.nonzero(labels == c)[:, 0]                         # this class, in the order the rule visits it
+        b = boxes[cand[pos]]
+        over = box_iou(b, b) > iou_thr
+        kc = torch.ones(pos.numel(), dtype=torch.bool, device=cand.device)
+        for i in range(pos.numel() - 1):
+            kc[i + 1:] &= ~(over[i, i + 1:] & kc[i])
+        keep[pos] = kc
+    sel = cand[keep]
+    if max_num > 0:
+        sel = sel[:max_num]
+    return torch.cat([boxes[sel], scores[sel, None]], 1), sel % C, sel
+
+
+def paste_masks(mask_prob, boxes, img_h, img_w, thr, return_float=False):
+    """_do_paste_mask(skip_empty=False) followed by `>= thr` (mmdet/models/roi_heads/mask_heads/fcn_mask_head.py:274-299, 306-377):
+    mask_prob [N, 28, 28] probabilities, boxes [N, 4] in the output image's pixels -> bool [N, img_h, img_w] (return_float: the sampled
+    float image instead).  Pixel centre (x + 0.5, y + 0.5) is mapped to the box's normalised coordinates, (p - lo) / (hi - lo) * 2 - 1,
+    and the mask sampled there bilinearly with grid_sample's align_corners=False geometry and zero padding.  Degenerate boxes as the
+    reference: an INFINITE normalised coordinate (a side of zero length) becomes 0, the mask's centre line.  A NaN coordinate (0 / 0: a
+    pixel centre exactly on such a side), which the reference hands to grid_sample, samples nothing here: the value is 0."""
+    N = mask_prob.shape[0]
+    dt = mask_prob.dtype if mask_prob.dtype == torch.float64 else torch.float32
+    boxes = boxes.to(dt)
+    x0, y0, x1, y1 = torch.split(boxes, 1, dim=1)
+    gy = (torch.arange(img_h, device=boxes.device, dtype=dt) + 0.5 - y0) / (y1 - y0) * 2 - 1     # [N, h]
+    gx = (torch.arange(img_w, device=boxes.device, dtype=dt) + 0.5 - x0) / (x1 - x0) * 2 - 1     # [N, w]
+    gy, gx = torch.where(torch.isinf(gy), torch.zeros_like(gy), gy), torch.where(torch.isinf(gx), torch.zeros_like(gx), gx)
+    dead = torch.isnan(gy)[:, :, None] | torch.isnan(gx)[:, None, :]
+    gy, gx = torch.nan_to_num(gy, nan=-3.0), torch.nan_to_num(gx, nan=-3.0)                        # outside the mask
+    grid = torch.stack([gx[:, None, :].expand(N, img_h, img_w), gy[:, :, None].expand(N, img_h, img_w)], 3)
+    img = F.grid_sample(mask_prob[:, None].to(dt), grid, mode="bilinear", padding_mode="zeros", align_corners=False)[:, 0]
+    img = torch.where(dead, torch.zeros_like(img), img)
+    return img if return_float else img >= thr
+
+
+def detect_post(rois, roi_count, cls, deltas, stds, img_hw, scale_factor, score_thr, iou_thr, K, dtype=torch.float32):
+    """The box half of the test-time post-processing of a batch, image by image through multiclass_nms (the definition of
+    ops.multiclass_nms_batch): rois [B, R, 4] of which the first roi_count[b] are proposals, cls [B, R, C + 1] logits, deltas [B, R, 4 C]
+    -> (boxes [B, K, 4], scores [B, K], labels long [B, K], count int32 [B], source int32 [B, K]), rows past count[b] zeros.  Softmax,
+    decode_deltas with stds clipped to img_hw, division by scale_factor [B, 4] unless None, multiclass_nms(score_thr, iou_thr, K).
+    dtype: the arithmetic (float64: the truth the GPU tests measure errors against)."""
+    B, R, C = cls.shape[0], cls.shape[1], cls.shape[2] - 1
+    dev = cls.device
+    boxes, scores = torch.zeros(B, K, 4, dtype=dtype, device=dev), torch.zeros(B, K, dtype=dtype, device=dev)
+    labels, source = torch.zeros(B, K, dtype=torch.long, device=dev), torch.zeros(B, K, dtype=torch.int32, device=dev)
+    count = torch.zeros(B, dtype=torch.int32, device=dev)
+    for b, n in enumerate(roi_count.tolist()):
+        n = max(0, min(int(n), R))
+        if n == 0:
+            continue
+        sc = F.softmax(cls[b, :n].to(dtype), dim=-1)
+        bx = decode_deltas_per_class(rois[b, :n].to(dtype), deltas[b, :n].to(dtype), stds, img_hw)
+        if scale_factor is not None:
+            bx = bx / scale_factor[b].to(dtype).repeat(C)
+        dets, lab, flat = multiclass_nms(bx, sc, score_thr, iou_thr, K)
+        k = dets.shape[0]
+        boxes[b, :k], scores[b, :k], labels[b, :k], source[b, :k], count[b] = dets[:, :4], dets[:, 4], lab, flat.to(torch.int32), k
+    return boxes, scores, labels, count, source
+
+
+def paste_masks_batch(mask_logits, labels, boxes, count, thr, out_hw):
+    """The mask half (the definition of ops.paste_masks): mask_logits [B K, C, 28, 28], labels long [B, K], boxes [B, K, 4], count [B] ->
+    uint8 [B, K, H, W]: paste_masks of sigmoid(the label's channel) for the first count[b] rows of image b, zeros behind them."""
+    B, K = labels.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    out = torch.zeros(B, K, H, W, dtype=torch.uint8, device=mask_logits.device)
+    lg = mask_logits.reshape(B, K, *mask_logits.shape[1:])
+    for b, n in enumerate(count.tolist()):
+        if n:
+            prob = lg[b, torch.arange(n, device=lg.device), labels[b, :n]].float().sigmoid()
+            out[b, :n] = paste_masks(prob, boxes[b, :n].float(), H, W, thr).to(torch.uint8)
+    return out
+
+
+class Detections:
+    """The detections of a batch in tensors of a fixed shape, the inference counterpart of PaddedTargets: boxes f32 [B, K, 4], scores f32
+    [B, K], labels int64 [B, K], count int32 [B] ON THE DEVICE (the first count[b] rows of image b are detections, in descending score;
+    the rest are zeros, masks included), source int32 [B, K] (the flat index r * C + c of each detection: proposal r, class c) and masks
+    uint8 [B, K, H, W] or None (Faster R-CNN)."""
+
+    def __init__(self, boxes, scores, labels, count, source, masks=None):
+        self.boxes, self.scores, self.labels, self.count, self.source, self.masks = boxes, scores, labels, count, source, masks
+
+    def as_lists(self):
+        """Per image (dets [k, 5], labels [k], masks bool [k, H, W] or None) -- reads the counts back: not for a captured step."""
+        out = []
+        for b, n in enumerate(self.count.tolist()):
+            dets = torch.cat([self.boxes[b, :n], self.scores[b, :n, None]], 1)
+            out.append((dets, self.labels[b, :n], None if self.masks is None else self.masks[b, :n].bool()))
+        return out
+
+
+def multiclass_nms_batch(rois, roi_count, cls, deltas, stds, img_hw, scale_factor, score_thr, iou_thr, K):
+    """detect_post for a batch.  On the GPU: HIP kernels for the whole batch that read the proposal counts from the device
+    (ops.multiclass_nms_batch -> pswin_multiclass_nms), so a captured call follows the buffers; on the CPU: the definition."""
+    if cls.is_cuda:
+        from . import ops
+        return ops.multiclass_nms_batch(rois, roi_count, cls, deltas, stds, img_hw, scale_factor, score_thr, iou_thr, K)
+    return detect_post(rois, roi_count, cls, deltas, stds, img_hw, scale_factor, score_thr, iou_thr, K)
+
+
+def paste_masks_dispatch(mask_logits, labels, boxes, count, thr, out_hw):
+    """paste_masks_batch.  On the GPU one HIP launch (ops.paste_masks -> pswin_paste_masks); on the CPU the definition."""
+    if mask_logits.is_cuda:
+        from . import ops
+        return ops.paste_masks(mask_logits, labels, boxes, count, thr, out_hw)
+    return paste_masks_batch(mask_logits, labels, boxes, count, thr, out_hw)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
 # neck and heads
 # ------------------------------------------------------------------------------------------------------------------------
 class _AddConvBias(torch.autograd.Function):
@@ -367,12 +512,17 @@ def roi_align(feats, strides, rois, out_size, finest_scale=56, sampling_ratio=0)
 # ------------------------------------------------------------------------------------------------------------------------
 class MiniMaskRCNN(nn.Module):
     """backbone -> FPN -> RPN -> RoI heads with the train_cfg numbers of configs/_base_/models/mask_rcnn_swin_fpn.py.
-    `heads_loss(feats, targets)` is everything behind the backbone; `forward_train` = backbone + heads_loss."""
+    `heads_loss(feats, targets)` is everything behind the backbone; `forward_train` = backbone + heads_loss.  At test time
+    `heads_predict(feats, img_hw)` is everything behind the backbone with the test_cfg numbers (mask_rcnn_swin_fpn.py:117-127) and
+    `simple_test` = backbone + heads_predict: a Detections."""
 
     STRIDES = (4, 8, 16, 32, 64)
     rand_like = staticmethod(torch.rand_like)    # the samplers' random keys (tests substitute a fixed sequence to compare eager and replayed steps)
     roi_align = staticmethod(roi_align)          # the HIP operator; tests of the head stand-ins on the CPU substitute the PyTorch statement
     assign = staticmethod(max_iou_assign_batch)  # the target assigner of a PaddedTargets batch (both stages, once per batch each)
+    multiclass_nms = staticmethod(multiclass_nms_batch)   # test time: softmax, decode, class-wise NMS, top K of a batch
+    paste = staticmethod(paste_masks_dispatch)            # test time: the detections' masks pasted into the image
+    BBOX_STDS = (0.1, 0.1, 0.2, 0.2)
 
     def __init__(self, backbone_cfg, num_classes=80):
         super().__init__()
@@ -385,6 +535,8 @@ class MiniMaskRCNN(nn.Module):
         self.num_classes = num_classes
         self.rpn_cfg = dict(pos=0.7, neg=0.3, min_pos=0.3, num=256, pos_fraction=0.5, nms_pre=2000, max_per_img=1000, nms=0.7)
         self.rcnn_cfg = dict(pos=0.5, num=512, pos_fraction=0.25, mask_size=28)
+        self.test_cfg = dict(rpn=dict(nms_pre=1000, max_per_img=1000, nms=0.7),
+                             rcnn=dict(score_thr=0.05, nms=0.5, max_per_img=100, mask_thr_binary=0.5))
         for part in (self.neck, self.rpn, self.mask_head):
             for m in part.modules():
                 if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
@@ -403,12 +555,39 @@ class MiniMaskRCNN(nn.Module):
         return [p for p in self.parameters() if id(p) not in bb]
 
     # -- RPN ----------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _rpn_flatten(rpn_outs):
+        """the RPN's outputs of all levels as f32 [B, A] scores and [B, A, 4] deltas, in the anchors' order"""
+        B = rpn_outs[0][0].shape[0]
+        cls_all = torch.cat([c.permute(0, 2, 3, 1).reshape(B, -1) for c, _ in rpn_outs], 1).float()          # [B, A]
+        reg_all = torch.cat([r.permute(0, 2, 3, 1).reshape(B, -1, 4) for _, r in rpn_outs], 1).float()       # [B, A, 4]
+        return cls_all, reg_all
+
+    @staticmethod
+    def _proposals(cls_b, reg_b, anchors, cfg, img_hw):
+        """The proposals of one image (no gradient; both the training and the test path, each with its own cfg): per level top nms_pre,
+        decode, NMS, then the best max_per_img over the levels -> (boxes [n, 4], scores [n]) in descending score.  A suppressed box
+        carries the score -1e4, so the survivors lead: (scores > -1e4).sum() of them."""
+        boxes_l, tops_l, at = [], [], 0
+        for a_l in anchors:
+            n = a_l.shape[0]
+            sc = cls_b[at:at + n]
+            k = min(cfg["nms_pre"], n)
+            top, ti = _topk_stable(sc, k)
+            boxes_l.append(decode_deltas(a_l[ti], reg_b[at:at + n][ti], (1.0, 1.0, 1.0, 1.0), img_hw))
+            tops_l.append(top)
+            at += n
+        keeps = nms_keep_groups(boxes_l, cfg["nms"])                   # the levels of one image: one launch on the GPU
+        scores_l = [torch.where(kp, top, top.new_full((), -1e4)) for kp, top in zip(keeps, tops_l)]
+        bx, sc = torch.cat(boxes_l), torch.cat(scores_l)
+        top, ti = _topk_stable(sc, min(cfg["max_per_img"], sc.numel()))
+        return bx[ti], top
+
     def _rpn_losses_and_proposals(self, rpn_outs, anchors, targets, img_hw):
         cfg = self.rpn_cfg
         B = rpn_outs[0][0].shape[0]
         flat_a = torch.cat(anchors, 0)
-        cls_all = torch.cat([c.permute(0, 2, 3, 1).reshape(B, -1) for c, _ in rpn_outs], 1).float()          # [B, A]
-        reg_all = torch.cat([r.permute(0, 2, 3, 1).reshape(B, -1, 4) for _, r in rpn_outs], 1).float()       # [B, A, 4]
+        cls_all, reg_all = self._rpn_flatten(rpn_outs)
         loss_cls = loss_reg = cls_all.new_zeros(())
         n_pos_max, n_tot = int(cfg["num"] * cfg["pos_fraction"]), cfg["num"]
         proposals = []
@@ -440,22 +619,8 @@ class MiniMaskRCNN(nn.Module):
             loss_cls = loss_cls + (F.binary_cross_entropy_with_logits(cls_all[b, idx], tgt, reduction="none") * valid).sum() / avg
             d_t = encode_deltas(flat_a[pos_rank], gt[arg[pos_rank]], (1.0, 1.0, 1.0, 1.0))
             loss_reg = loss_reg + ((reg_all[b, pos_rank] - d_t).abs().sum(1) * pos_valid.float()).sum() / avg
-            # proposals (no gradient): per level top nms_pre, decode, NMS, then the best max_per_img over the levels
             with torch.no_grad():
-                boxes_l, tops_l, at = [], [], 0
-                for a_l in anchors:
-                    n = a_l.shape[0]
-                    sc = cls_all[b, at:at + n]
-                    k = min(cfg["nms_pre"], n)
-                    top, ti = _topk_stable(sc, k)
-                    boxes_l.append(decode_deltas(a_l[ti], reg_all[b, at:at + n][ti], (1.0, 1.0, 1.0, 1.0), img_hw))
-                    tops_l.append(top)
-                    at += n
-                keeps = nms_keep_groups(boxes_l, cfg["nms"])                   # the levels of one image: one launch on the GPU
-                scores_l = [torch.where(kp, top, top.new_full((), -1e4)) for kp, top in zip(keeps, tops_l)]
-                bx, sc = torch.cat(boxes_l), torch.cat(scores_l)
-                ti = _topk_stable(sc, min(cfg["max_per_img"], sc.numel()))[1]
-                proposals.append(bx[ti])
+                proposals.append(self._proposals(cls_all[b], reg_all[b], anchors, cfg, img_hw)[0])
         return loss_cls / B, loss_reg / B, proposals
 
     # -- RoI heads ------------------------------------------------------------------------------------------------------
@@ -556,6 +721,56 @@ class MiniMaskRCNN(nn.Module):
 
     def forward_train(self, img, targets):
         return self.heads_loss(self.backbone(img), targets, img.shape[2:])
+
+    # -- inference ------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def heads_predict(self, feats, img_hw, scale_factor=None, rescale=False, with_masks=True, return_raw=False, ori_hw=None):
+        """Everything behind the backbone at test time (two_stage.py:217 simple_test; test_mixins.py simple_test_bboxes / simple_test_mask):
+        a Detections with K = test_cfg rcnn max_per_img rows per image.  scale_factor: f32 [B, 4] device tensor (w, h, w, h) or None.
+        rescale=True: the boxes are divided by it before the NMS, as the reference does, and multiplied back to form the mask RoIs; the
+        masks are then pasted at ori_hw (one size for the batch), otherwise at img_hw.  with_masks=False: the Faster R-CNN result.
+        return_raw=True: also a dict of the tensors the post-processing consumed -- rois [B, R, 4], roi_count [B], cls [B, R, C + 1],
+        deltas [B, R, 4 C], mask_logits [B K, C, 28, 28] -- so that the definitions can be applied to exactly those.
+        No host synchronisation, no host-to-device copy, no data-dependent shape: the call can be captured and replayed."""
+        from ._lib import PswinError
+        if rescale and (scale_factor is None or (with_masks and ori_hw is None)):
+            raise PswinError("heads_predict: rescale=True needs scale_factor [B, 4] and, with masks, ori_hw=(H, W)")
+        rpn_cfg, cfg = self.test_cfg["rpn"], self.test_cfg["rcnn"]
+        if self.channels_last:
+            feats = [f.contiguous(memory_format=torch.channels_last) for f in feats]
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):
+            fpn = self.neck([f for f in feats])
+            rpn_outs = self.rpn(fpn)
+        anchors = make_anchors([f.shape[2:] for f in fpn], self.STRIDES, feats[0].device)
+        cls_all, reg_all = self._rpn_flatten(rpn_outs)
+        B, C, K = cls_all.shape[0], self.num_classes, cfg["max_per_img"]
+        props = [self._proposals(cls_all[b], reg_all[b], anchors, rpn_cfg, img_hw) for b in range(B)]
+        rois = torch.stack([p[0] for p in props])                                                 # [B, R, 4]
+        roi_count = (torch.stack([p[1] for p in props]) > -1e4).sum(1).to(torch.int32)            # the survivors of the RPN's NMS lead
+        R = rois.shape[1]
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):
+            x = self.roi_align(fpn[:4], self.STRIDES[:4], rois, 7)
+            cls, reg = self.bbox_head(x.to(feats[0].dtype))
+        cls, reg = cls.view(B, R, C + 1), reg.view(B, R, 4 * C)
+        sf = scale_factor if rescale else None
+        boxes, scores, labels, count, source = self.multiclass_nms(rois, roi_count, cls, reg, self.BBOX_STDS, img_hw, sf, cfg["score_thr"],
+                                                                   cfg["nms"], K)
+        masks = mask_logits = None
+        if with_masks:
+            mask_rois = boxes * sf[:, None, :] if rescale else boxes                              # back at the test scale (test_mixins.py:275-281)
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):
+                xm = self.roi_align(fpn[:4], self.STRIDES[:4], mask_rois, 14)
+                mask_logits = self.mask_head(xm.to(feats[0].dtype))                               # [B * K, classes, 28, 28]
+            masks = self.paste(mask_logits, labels, boxes, count, cfg["mask_thr_binary"], ori_hw if rescale else img_hw)
+        out = Detections(boxes, scores, labels, count, source, masks)
+        if return_raw:
+            return out, dict(rois=rois, roi_count=roi_count, cls=cls, deltas=reg, mask_logits=mask_logits)
+        return out
+
+    @torch.no_grad()
+    def simple_test(self, img, **kw):
+        """backbone + heads_predict (TwoStageDetector.simple_test): a Detections for the batch"""
+        return self.heads_predict(self.backbone(img), img.shape[2:], **kw)
 
 
 def synthetic_targets(batch, H, W, device, num_classes=80, seed=0):

@@ -1576,6 +1576,90 @@ def max_iou_assign_batch(cand, gt, gt_count, pos_iou_thr, neg_iou_thr, min_pos_i
     return inds, miou
 
 
+def _lowp_or_f32(t):
+    return t if t.dtype in (torch.float32, torch.bfloat16) else t.float()
+
+
+def multiclass_nms_batch(rois, roi_count, cls, deltas, stds, img_hw, scale_factor, score_thr, iou_thr, K):
+    """detector.detect_post for a batch on the GPU (pswin_multiclass_nms_scores -> sort -> pswin_multiclass_nms -> sort ->
+    pswin_multiclass_nms_select): (boxes f32 [B, K, 4], scores f32 [B, K], labels int64 [B, K], count int32 [B], source int32 [B, K]).
+    rois f32 [B, R, 4]; roi_count int32 [B] ON THE DEVICE; cls [B, R, C + 1] and deltas [B, R, 4 C] logits, f32 or bf16; scale_factor
+    f32 [B, 4] or None.  R <= 1024, C <= 128, K <= 1024.  The two sorts are torch's stable sorts, per (image, class) list and per image;
+    no host-to-device copy and no host synchronisation, so the call can be captured.  CPU tensors: the definition."""
+    if not cls.is_cuda:
+        from . import detector
+        return detector.detect_post(rois, roi_count, cls, deltas, stds, img_hw, scale_factor, score_thr, iou_thr, K)
+    if cls.dim() != 3 or rois.dim() != 3 or deltas.dim() != 3 or rois.shape[2] != 4 or rois.shape[:2] != cls.shape[:2] or \
+            deltas.shape[:2] != cls.shape[:2] or deltas.shape[2] != 4 * (cls.shape[2] - 1):
+        raise PswinError(f"multiclass_nms_batch: rois [B, R, 4], cls [B, R, C + 1], deltas [B, R, 4 C], got {tuple(rois.shape)}, "
+                         f"{tuple(cls.shape)}, {tuple(deltas.shape)}")
+    B, R, C = int(cls.shape[0]), int(cls.shape[1]), int(cls.shape[2]) - 1
+    dev = cls.device
+    if roi_count.dtype != torch.int32 or tuple(roi_count.shape) != (B,) or roi_count.device != dev:
+        raise PswinError("multiclass_nms_batch: roi_count must be an int32 [B] tensor on the device of the logits")
+    if scale_factor is not None and (scale_factor.dtype != torch.float32 or tuple(scale_factor.shape) != (B, 4) or scale_factor.device != dev):
+        raise PswinError("multiclass_nms_batch: scale_factor must be an f32 [B, 4] tensor on the device of the logits, or None")
+    rois, roi_count = rois.detach().float().contiguous(), roi_count.contiguous()
+    cls, deltas = _lowp_or_f32(cls.detach()).contiguous(), _lowp_or_f32(deltas.detach()).contiguous()
+    scale = None if scale_factor is None else scale_factor.contiguous()
+    nbytes = int(_lib.load().pswin_multiclass_nms_workspace(B, R, C))
+    _lib.check(min(nbytes, 0), "pswin_multiclass_nms_workspace")
+    key = ("detect_ws", B, R, C, _dev_key(dev))
+    if key not in _CACHE:
+        _CACHE[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    std4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    stdp = ctypes.cast(std4, ctypes.c_void_p)
+    H, W = int(img_hw[0]), int(img_hw[1])
+    keys = torch.empty(B, C, R, dtype=torch.float32, device=dev)
+    call("pswin_multiclass_nms_scores", cls, ptr(cls), dtype_code(cls), ptr(roi_count), B, R, C, ctypes.c_float(float(score_thr)), ptr(keys))
+    skeys, sidx = torch.sort(keys, dim=-1, descending=True, stable=True)                  # equal scores: ascending proposal
+    final = torch.empty(B, R * C, dtype=torch.float32, device=dev)
+    call("pswin_multiclass_nms", cls, ptr(skeys), ptr(sidx), ptr(rois), ptr(deltas), dtype_code(deltas), stdp, H, W, ptr(scale), B, R, C,
+         ctypes.c_float(float(iou_thr)), ptr(final), ptr(_CACHE[key]))
+    tkeys, tidx = torch.sort(final, dim=-1, descending=True, stable=True)                 # equal scores: ascending r * C + c
+    K = int(K)
+    boxes = torch.empty(B, K, 4, dtype=torch.float32, device=dev)
+    scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+    labels = torch.empty(B, K, dtype=torch.int64, device=dev)
+    source = torch.empty(B, K, dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    call("pswin_multiclass_nms_select", cls, ptr(tkeys), ptr(tidx), R * C, min(K, R * C), ptr(rois), ptr(deltas), dtype_code(deltas), stdp, H, W,
+         ptr(scale), B, R, C, K, ptr(boxes), ptr(scores), ptr(labels), ptr(source), ptr(count))
+    return boxes, scores, labels, count, source
+
+
+def paste_masks(mask_logits, labels, boxes, count, thr, out_hw, out=None):
+    """detector.paste_masks_batch on the GPU in one launch (pswin_paste_masks): uint8 [B, K, H, W].  mask_logits [B K, C, 28, 28], f32 or
+    bf16, in any dense layout (its strides are passed on: the mask head's channels-last output is read in place); labels int64 [B, K];
+    boxes f32 [B, K, 4] in the output image's pixels; count int32 [B] ON THE DEVICE.  Every byte of the output is written (zeros behind
+    count[b]), so `out` may be a buffer that is reused.  CPU tensors: the definition."""
+    if not mask_logits.is_cuda:
+        from . import detector
+        res = detector.paste_masks_batch(mask_logits, labels, boxes, count, thr, out_hw)
+        return res if out is None else out.copy_(res)
+    H, W = int(out_hw[0]), int(out_hw[1])
+    if labels.dim() != 2 or mask_logits.dim() != 4 or tuple(mask_logits.shape[2:]) != (28, 28) or mask_logits.shape[0] != labels.numel() or \
+            tuple(boxes.shape) != tuple(labels.shape) + (4,):
+        raise PswinError(f"paste_masks: mask_logits [B K, C, 28, 28], labels [B, K], boxes [B, K, 4], got {tuple(mask_logits.shape)}, "
+                         f"{tuple(labels.shape)}, {tuple(boxes.shape)}")
+    B, K, C = int(labels.shape[0]), int(labels.shape[1]), int(mask_logits.shape[1])
+    dev = mask_logits.device
+    if count.dtype != torch.int32 or tuple(count.shape) != (B,) or count.device != dev or labels.dtype != torch.int64:
+        raise PswinError("paste_masks: count must be an int32 [B] tensor on the device of the logits, labels int64")
+    lg = _lowp_or_f32(mask_logits.detach())
+    if min(lg.stride()) < 1:
+        lg = lg.contiguous()
+    labels, boxes, count = labels.contiguous(), boxes.detach().float().contiguous(), count.contiguous()
+    if out is None:
+        out = torch.empty(B, K, H, W, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, K, H, W) or not out.is_contiguous() or out.device != dev:
+        raise PswinError(f"paste_masks: out must be a contiguous uint8 [{B}, {K}, {H}, {W}] tensor on the device of the logits")
+    sn, sc, sy, sx = (int(v) for v in lg.stride())
+    call("pswin_paste_masks", lg, ptr(lg), dtype_code(lg), sn, sc, sy, sx, ptr(labels), ptr(boxes), ptr(count), B, K, C, H, W,
+         ctypes.c_float(float(thr)), ptr(out), algo_bytes=B * K * H * W)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # qkv Linear + attention core in one kernel for C = 192 / 384 (pswin_qkv_attn_fused_fwd, round 3)
 # ------------------------------------------------------------------------------------------------
