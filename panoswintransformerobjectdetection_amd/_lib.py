@@ -89,6 +89,12 @@ _PROTOTYPES = {
     "pswin_multiclass_nms_select": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pswin_paste_masks": [_vp, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                           _f, _vp, _vp],
+    "pswin_sample_rows_per_workgroup": [],
+    "pswin_sample_workspace": [_i, _i, _i],
+    "pswin_sample_ranks": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "pswin_rpn_targets": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "pswin_roi_targets": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pswin_mask_targets": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
     "pswin_gemm_nt_supported": [ctypes.c_longlong, _i, _i],
     "pswin_gemm_nt": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],
     "pswin_gemm_nt_f32": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],

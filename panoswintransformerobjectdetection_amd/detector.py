@@ -20,7 +20,9 @@ head operators are ordinary PyTorch-ROCm operators (MIOpen / hipBLASLt, bf16 aut
 TARGETS: a list of dicts per image (shapes tied to one batch), or a PaddedTargets (fixed shapes, the box count of every image on the
 device: the form a captured step is replayed on with the next batch's annotations).  With a PaddedTargets both stages' MaxIoUAssigner
 run as HIP kernels for the whole batch (max_iou_assign_batch -> pswin_max_iou_assign), pinned to the reference's own results
-(tests/golden/max_iou_assign_batch.npz).
+(tests/golden/max_iou_assign_batch.npz), and so does everything between "assigned" and "loss", once per batch: the RandomSampler with a
+defined tie order, the box targets and the mask targets (sample_ranks, rpn_targets, roi_targets, mask_targets below are the definitions;
+ops.rpn_targets / roi_targets / mask_targets -> csrc/pswin_targets.hip).
 
 INFERENCE: `heads_predict` / `simple_test` (TwoStageDetector.simple_test, mmdet/models/detectors/two_stage.py:217) return a Detections:
 fixed shapes, the detection count of every image on the device, no host synchronisation -- one captured graph serves every batch.  The
@@ -179,6 +181,127 @@ def max_iou_assign_batch(cand, gt, gt_count, pos, neg, min_pos, match_low_qualit
         inds[b, valid] = max_iou_assign(c[valid], gt[b, :G], pos, neg, min_pos, match_low_quality)
         best[b, valid] = box_iou(gt[b, :G], c[valid]).max(0)[0]
     return inds, best
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# sampling, box targets and mask targets of a padded batch (the definitions; on the GPU: csrc/pswin_targets.hip through ops)
+# ------------------------------------------------------------------------------------------------------------------------
+def sample_ranks(gt_inds, key, n_pos, n_neg):
+    """RandomSampler with static shapes for a batch: gt_inds long [B, N] (an assigner's result), key f32 [B, N] (finite, >= 0) ->
+    (pos_rank long [B, n_pos], neg_rank long [B, n_neg]), n_pos, n_neg <= N.  A candidate that does not belong to a list goes BEHIND
+    its members: behind = where(gt_inds < 0, key + 4, key + 2) in float32 (ignored rows, the gt padding among them, behind everything).
+    pos_rank is the order of where(gt_inds > 0, key, behind), neg_rank that of where(gt_inds == 0, key, behind), first columns only.
+
+    TIES.  The sort is STABLE: equal composed keys come out in ascending index, the choice _topk_stable makes and for the same reason
+    (a captured graph, its replays and the definition must agree on the bit).  The order is that of the float32 COMPOSED key fl(key + 2),
+    which keeps 2^-22 of the key's 2^-24 resolution, not that of `key`: so every outcome is one an unstable argsort of the same composed
+    keys could have produced."""
+    N = gt_inds.shape[1]
+    if n_pos > N or n_neg > N:
+        raise ValueError(f"sample_ranks: n_pos = {n_pos} and n_neg = {n_neg} must not exceed the {N} candidates")
+    key = key.float()
+    behind = torch.where(gt_inds < 0, key + 4, key + 2)
+    pos_rank = torch.sort(torch.where(gt_inds > 0, key, behind), dim=1, stable=True)[1][:, :n_pos]
+    neg_rank = torch.sort(torch.where(gt_inds == 0, key, behind), dim=1, stable=True)[1][:, :n_neg]
+    return pos_rank, neg_rank
+
+
+def _encode_rows(src, dst, stds, ok):
+    """encode_deltas on [B, P, 4] rows, rows whose `ok` is false ZERO (a loss multiplies them by 0)"""
+    d = encode_deltas(src.reshape(-1, 4), dst.reshape(-1, 4), stds).reshape(src.shape)
+    return torch.where(ok[..., None], d, torch.zeros_like(d))
+
+
+def rpn_targets(gt_inds, key, anchors, gt, n_pos_max, n_tot):
+    """The RPN's sampled targets of a padded batch: gt_inds long [B, A], key f32 [B, A], anchors f32 [A, 4] (shared), gt f32 [B, Gmax, 4]
+    -> (idx long [B, n_pos_max + n_tot], valid f32 of that shape, pos_valid bool [B, n_pos_max], reg_t f32 [B, n_pos_max, 4]).
+    idx = (pos_rank, neg_rank) of sample_ranks(gt_inds, key, n_pos_max, n_tot); a positive slot is valid when it holds a positive, a
+    negative slot when it holds a negative AND lies in front of n_tot - (the number of valid positives); reg_t =
+    encode_deltas(anchors[pos_rank], gt[(gt_inds - 1).clamp(min=0)[pos_rank]], stds 1), rows of invalid positive slots zero."""
+    B = gt_inds.shape[0]
+    pos_rank, neg_rank = sample_ranks(gt_inds, key, n_pos_max, n_tot)
+    pos_valid = gt_inds.gather(1, pos_rank) > 0
+    n_pos = pos_valid.sum(1, keepdim=True)
+    neg_valid = (gt_inds.gather(1, neg_rank) == 0) & (torch.arange(n_tot, device=key.device)[None] < (n_tot - n_pos))
+    arg = (gt_inds - 1).clamp(min=0).gather(1, pos_rank)
+    dst = gt[torch.arange(B, device=gt.device)[:, None], arg]
+    reg_t = _encode_rows(anchors[pos_rank], dst, (1.0, 1.0, 1.0, 1.0), pos_valid)
+    return torch.cat([pos_rank, neg_rank], 1), torch.cat([pos_valid, neg_valid], 1).float(), pos_valid, reg_t
+
+
+def roi_targets(gt_inds, key, cand, gt, gt_labels, num_classes, n_pos_max, n_tot, stds):
+    """The RoI head's sampled RoIs and targets of a padded batch: gt_inds long [B, N], key f32 [B, N], cand f32 [B, N, 4], gt f32
+    [B, Gmax, 4], gt_labels long [B, Gmax] -> (rois f32 [B, n_tot, 4], labels long [B, n_tot], reg_t f32 [B, n_pos_max, 4], pos_valid bool
+    [B, n_pos_max], gt_idx long [B, n_pos_max]).  The first n_pos_max RoIs are pos_rank of sample_ranks(gt_inds, key, n_pos_max, n_tot).
+    The positive slots that found no positive were filled with the lowest-key non-positives (they count as background): the negatives
+    proper are the NEXT ones of the negative order, neg_order[(j + filler).clamp(max=N - 1)] with filler = n_pos_max - (valid positives),
+    so that no RoI is sampled twice.  labels: the matched gt's label in a valid positive slot, num_classes (background) elsewhere;
+    gt_idx = (gt_inds - 1).clamp(min=0)[pos_rank]; reg_t = encode_deltas(rois, gt[gt_idx], stds), rows of invalid slots zero."""
+    B, N = gt_inds.shape
+    bi = torch.arange(B, device=gt.device)[:, None]
+    pos_rank, neg_order = sample_ranks(gt_inds, key, n_pos_max, n_tot)
+    pos_valid = gt_inds.gather(1, pos_rank) > 0
+    filler = n_pos_max - pos_valid.sum(1, keepdim=True)
+    take = (torch.arange(n_tot - n_pos_max, device=key.device)[None] + filler).clamp(max=N - 1)    # < n_tot: inside neg_order
+    idx = torch.cat([pos_rank, neg_order.gather(1, take)], 1)
+    rois = cand[bi, idx]
+    gt_idx = (gt_inds - 1).clamp(min=0).gather(1, pos_rank)
+    labels = torch.full_like(idx, num_classes)
+    labels[:, :n_pos_max] = torch.where(pos_valid, gt_labels.gather(1, gt_idx), labels[:, :n_pos_max])
+    reg_t = _encode_rows(rois[:, :n_pos_max], gt[bi, gt_idx], stds, pos_valid)
+    return rois, labels, reg_t, pos_valid, gt_idx
+
+
+def mask_targets(masks, rois, gt_idx, pos_valid, size=28, dtype=torch.float32, return_float=False):
+    """The mask head's targets of a padded batch: masks uint8 [B, Gmax, H, W], rois f32 [B, P, 4] in image pixels, gt_idx long [B, P],
+    pos_valid bool [B, P] -> f32 [B * P, size, size] of 0 / 1 (return_float: the sampled float image instead).  Sample point (i, j) of a
+    RoI lies at t = (j + 0.5) / size along its sides, in normalised coordinates gx = (x0 + (x1 - x0) * t) / W * 2 - 1; the ONE assigned
+    bitmap masks[b, gt_idx[b, p]] is sampled there bilinearly with grid_sample's align_corners=False geometry and zero padding, then
+    `>= 0.5`.  Rows whose pos_valid is false are zeros (the loss masks them).  dtype: the arithmetic (float64: the truth the GPU test
+    measures the near-threshold set against).
+
+    PARITY: unpinned.  The reference's BitmapMasks.crop_and_resize calls mmcv.ops.roi_align, which the reference tree does not contain,
+    so nothing pins these targets to the reference's."""
+    B, G, H, W = masks.shape
+    P = rois.shape[1]
+    t = (torch.arange(size, device=rois.device, dtype=dtype) + 0.5) / size
+    out = []
+    for b in range(B):
+        r = rois[b].to(dtype)
+        gx = (r[:, 0:1] + (r[:, 2:3] - r[:, 0:1]) * t[None]) / W * 2 - 1
+        gy = (r[:, 1:2] + (r[:, 3:4] - r[:, 1:2]) * t[None]) / H * 2 - 1
+        grid = torch.stack([gx[:, None, :].expand(-1, size, size), gy[:, :, None].expand(-1, size, size)], -1)   # [P, size, size, 2]
+        plane = masks[b][gt_idx[b].clamp(0, G - 1)].to(dtype)[:, None]                                         # [P, 1, H, W]
+        smp = F.grid_sample(plane, grid, mode="bilinear", padding_mode="zeros", align_corners=False)[:, 0]
+        out.append(torch.where(pos_valid[b][:, None, None], smp, torch.zeros_like(smp)))
+    img = torch.cat(out)
+    return img if return_float else (img >= 0.5).float()
+
+
+def rpn_targets_dispatch(gt_inds, key, anchors, gt, n_pos_max, n_tot):
+    """rpn_targets.  On the GPU: HIP kernels for the whole batch (ops.rpn_targets -> pswin_sample_ranks, pswin_rpn_targets); on the CPU
+    the definition."""
+    if gt_inds.is_cuda:
+        from . import ops
+        return ops.rpn_targets(gt_inds, key, anchors, gt, n_pos_max, n_tot)
+    return rpn_targets(gt_inds, key, anchors, gt, n_pos_max, n_tot)
+
+
+def roi_targets_dispatch(gt_inds, key, cand, gt, gt_labels, num_classes, n_pos_max, n_tot, stds):
+    """roi_targets.  On the GPU: HIP kernels for the whole batch (ops.roi_targets -> pswin_sample_ranks, pswin_roi_targets); on the CPU
+    the definition."""
+    if gt_inds.is_cuda:
+        from . import ops
+        return ops.roi_targets(gt_inds, key, cand, gt, gt_labels, num_classes, n_pos_max, n_tot, stds)
+    return roi_targets(gt_inds, key, cand, gt, gt_labels, num_classes, n_pos_max, n_tot, stds)
+
+
+def mask_targets_dispatch(masks, rois, gt_idx, pos_valid, size=28):
+    """mask_targets.  On the GPU one HIP launch (ops.mask_targets -> pswin_mask_targets); on the CPU the definition."""
+    if masks.is_cuda:
+        from . import ops
+        return ops.mask_targets(masks, rois, gt_idx, pos_valid, size)
+    return mask_targets(masks, rois, gt_idx, pos_valid, size)
 
 
 class PaddedTargets:
@@ -520,6 +643,9 @@ class MiniMaskRCNN(nn.Module):
     rand_like = staticmethod(torch.rand_like)    # the samplers' random keys (tests substitute a fixed sequence to compare eager and replayed steps)
     roi_align = staticmethod(roi_align)          # the HIP operator; tests of the head stand-ins on the CPU substitute the PyTorch statement
     assign = staticmethod(max_iou_assign_batch)  # the target assigner of a PaddedTargets batch (both stages, once per batch each)
+    rpn_targets = staticmethod(rpn_targets_dispatch)      # PaddedTargets: the RPN's sampler and box targets, once per batch
+    roi_targets = staticmethod(roi_targets_dispatch)      # PaddedTargets: the RoI head's sampler, RoIs, labels and box targets, once per batch
+    mask_targets = staticmethod(mask_targets_dispatch)    # PaddedTargets: the mask head's targets, once per batch
     multiclass_nms = staticmethod(multiclass_nms_batch)   # test time: softmax, decode, class-wise NMS, top K of a batch
     paste = staticmethod(paste_masks_dispatch)            # test time: the detections' masks pasted into the image
     BBOX_STDS = (0.1, 0.1, 0.2, 0.2)
@@ -594,19 +720,31 @@ class MiniMaskRCNN(nn.Module):
         padded = isinstance(targets, PaddedTargets)
         if padded:                                                                                # the anchors are shared by the images
             inds_all = self.assign(flat_a, targets.boxes, targets.count, cfg["pos"], cfg["neg"], cfg["min_pos"], True)[0]
+            # assign, sample and encode once per batch (rpn_targets); the keys are drawn per image, as the list form draws them
+            proto = cls_all.new_empty(flat_a.shape[0])
+            key = torch.stack([self.rand_like(proto) for _ in range(B)])
+            idx, valid, pos_valid, d_t = self.rpn_targets(inds_all, key, flat_a, targets.boxes, n_pos_max, n_tot)
+            tgt = torch.cat([torch.ones(n_pos_max, device=key.device), torch.zeros(n_tot, device=key.device)])
+            avg = valid.sum(1).clamp(min=1)                                                       # [B]
+            bce = F.binary_cross_entropy_with_logits(cls_all.gather(1, idx), tgt[None].expand(B, -1), reduction="none")
+            l_cls = (bce * valid).sum(1) / avg
+            reg_p = reg_all.gather(1, idx[:, :n_pos_max, None].expand(-1, -1, 4))
+            l_reg = ((reg_p - d_t).abs().sum(2) * pos_valid.float()).sum(1) / avg
+            for b in range(B):                                                                    # per image, then over the batch in image order
+                loss_cls, loss_reg = loss_cls + l_cls[b], loss_reg + l_reg[b]
+                with torch.no_grad():
+                    proposals.append(self._proposals(cls_all[b], reg_all[b], anchors, cfg, img_hw)[0])
+            return loss_cls / B, loss_reg / B, proposals
         for b in range(B):
             # MaxIoUAssigner(pos 0.7, neg 0.3, min_pos 0.3, match_low_quality) -- configs/_base_/models/mask_rcnn_swin_fpn.py:79-85
-            if padded:
-                gt, gt_inds = targets.boxes[b], inds_all[b]                                       # [Gmax, 4]: rows past the count are never matched
-            else:
-                gt = targets[b]["boxes"]
-                gt_inds = max_iou_assign(flat_a, gt, cfg["pos"], cfg["neg"], cfg["min_pos"], True)
+            gt = targets[b]["boxes"]
+            gt_inds = max_iou_assign(flat_a, gt, cfg["pos"], cfg["neg"], cfg["min_pos"], True)
             label = gt_inds.clamp(max=1).to(flat_a.dtype)                                         # 1 positive, 0 negative, -1 neither
             arg = (gt_inds - 1).clamp(min=0)
             best = label
             # random sampling with static shapes: rank by a random key, positives first
             key = self.rand_like(best)
-            behind = torch.where(label < 0, key + 4, key + 2) if padded else key + 2              # padded: ignored behind everything
+            behind = key + 2
             pos_rank = torch.argsort(torch.where(label == 1, key, behind))[:n_pos_max]
             pos_valid = label[pos_rank] == 1
             neg_rank = torch.argsort(torch.where(label == 0, key, behind))[:n_tot]
@@ -624,58 +762,65 @@ class MiniMaskRCNN(nn.Module):
         return loss_cls / B, loss_reg / B, proposals
 
     # -- RoI heads ------------------------------------------------------------------------------------------------------
+    def _roi_targets_lists(self, proposals, targets, n_pos_max, n_tot):
+        """The RoI head's sampler and targets for the list form of the targets, image by image: (rois [B, n_tot, 4], labels [B * n_tot],
+        reg_t [B * n_pos_max, 4], pos_valid as f32 [B * n_pos_max], per image gt_idx [n_pos_max])"""
+        cfg = self.rcnn_cfg
+        rois, labels, reg_t, pos_valid_all, gt_idx_all = [], [], [], [], []
+        for b, props in enumerate(proposals):
+            # MaxIoUAssigner(pos 0.5, neg 0.5, min_pos 0.5, match_low_quality=True) -- mask_rcnn_swin_fpn.py:101-107
+            gt, gl = targets[b]["boxes"], targets[b]["labels"]
+            cand = torch.cat([gt, props], 0)                                                      # add_gt_as_proposals
+            gt_inds = max_iou_assign(cand, gt, cfg["pos"], cfg["pos"], cfg["pos"], True)
+            is_pos, arg = gt_inds > 0, (gt_inds - 1).clamp(min=0)
+            best = is_pos.float()
+            key = self.rand_like(best)
+            behind = key + 2
+            pos_rank = torch.argsort(torch.where(is_pos, key, behind))[:n_pos_max]
+            pos_valid = is_pos[pos_rank]
+            # the positive slots that found no positive were filled with the lowest-key non-positives (they count as background
+            # below): the negatives proper are the NEXT ones in that order, so that no RoI is sampled twice
+            filler = n_pos_max - pos_valid.sum()
+            neg_order = torch.argsort(torch.where(~is_pos, key, behind))
+            take = (torch.arange(n_tot - n_pos_max, device=key.device) + filler).clamp(max=neg_order.numel() - 1)
+            neg_rank = neg_order[take]
+            idx = torch.cat([pos_rank, neg_rank])
+            rois.append(cand[idx])
+            lab = torch.where(torch.cat([pos_valid, torch.zeros_like(neg_rank, dtype=torch.bool)]), gl[arg[idx]],
+                              torch.full_like(idx, self.num_classes))                              # background = num_classes
+            labels.append(lab)
+            reg_t.append(encode_deltas(cand[pos_rank], gt[arg[pos_rank]], (0.1, 0.1, 0.2, 0.2)))
+            pos_valid_all.append(pos_valid)
+            gt_idx_all.append(arg[pos_rank])
+        return torch.stack(rois), torch.cat(labels), torch.cat(reg_t), torch.cat(pos_valid_all).float(), gt_idx_all
+
     def _roi_losses(self, feats, proposals, targets, img_hw):
         cfg = self.rcnn_cfg
         n_tot, n_pos_max = cfg["num"], int(cfg["num"] * cfg["pos_fraction"])
-        rois, labels, reg_t, pos_valid_all, gt_idx_all = [], [], [], [], []
         padded = isinstance(targets, PaddedTargets)
         with torch.no_grad():
             if padded:                                                                            # add_gt_as_proposals: the padded gt rows lead
                 cand_all = torch.cat([targets.boxes, torch.stack(proposals)], 1)
                 inds_all = self.assign(cand_all, targets.boxes, targets.count, cfg["pos"], cfg["pos"], cfg["pos"], True,
                                        lead_gt=targets.max_gt)[0]
-            for b, props in enumerate(proposals):
-                # MaxIoUAssigner(pos 0.5, neg 0.5, min_pos 0.5, match_low_quality=True) -- mask_rcnn_swin_fpn.py:101-107
-                if padded:
-                    gt, gl, cand, gt_inds = targets.boxes[b], targets.labels[b], cand_all[b], inds_all[b]
-                else:
-                    gt, gl = targets[b]["boxes"], targets[b]["labels"]
-                    cand = torch.cat([gt, props], 0)                                              # add_gt_as_proposals
-                    gt_inds = max_iou_assign(cand, gt, cfg["pos"], cfg["pos"], cfg["pos"], True)
-                is_pos, arg = gt_inds > 0, (gt_inds - 1).clamp(min=0)
-                best = is_pos.float()
-                key = self.rand_like(best)
-                # padded: the negatives are gt_inds == 0, and the ignored rows (the gt padding) sort behind everything in both orders,
-                # so that a padding row is never drawn as a RoI or as a background filler
-                is_neg = gt_inds == 0 if padded else ~is_pos
-                behind = torch.where(gt_inds < 0, key + 4, key + 2) if padded else key + 2
-                pos_rank = torch.argsort(torch.where(is_pos, key, behind))[:n_pos_max]
-                pos_valid = is_pos[pos_rank]
-                # the positive slots that found no positive were filled with the lowest-key non-positives (they count as background
-                # below): the negatives proper are the NEXT ones in that order, so that no RoI is sampled twice
-                filler = n_pos_max - pos_valid.sum()
-                neg_order = torch.argsort(torch.where(is_neg, key, behind))
-                take = (torch.arange(n_tot - n_pos_max, device=key.device) + filler).clamp(max=neg_order.numel() - 1)
-                neg_rank = neg_order[take]
-                idx = torch.cat([pos_rank, neg_rank])
-                rois.append(cand[idx])
-                lab = torch.where(torch.cat([pos_valid, torch.zeros_like(neg_rank, dtype=torch.bool)]), gl[arg[idx]],
-                                  torch.full_like(idx, self.num_classes))                          # background = num_classes
-                labels.append(lab)
-                reg_t.append(encode_deltas(cand[pos_rank], gt[arg[pos_rank]], (0.1, 0.1, 0.2, 0.2)))
-                pos_valid_all.append(pos_valid)
-                gt_idx_all.append(arg[pos_rank])
-        rois_b, labels_c = torch.stack(rois), torch.cat(labels)                                  # [B, n_tot, 4], [B * n_tot]
+                # the negatives are gt_inds == 0, and the ignored rows (the gt padding) sort behind everything in both orders, so that a
+                # padding row is never drawn as a RoI or as a background filler (sample_ranks); once per batch, the keys drawn per image
+                proto = cand_all.new_empty(cand_all.shape[1])
+                key = torch.stack([self.rand_like(proto) for _ in proposals])
+                rois_b, labels_b, reg_t, pos_valid, gt_idx = self.roi_targets(inds_all, key, cand_all, targets.boxes, targets.labels,
+                                                                              self.num_classes, n_pos_max, n_tot, (0.1, 0.1, 0.2, 0.2))
+                labels_c, reg_t, pv = labels_b.reshape(-1), reg_t.reshape(-1, 4), pos_valid.reshape(-1).float()
+            else:
+                rois_b, labels_c, reg_t, pv, gt_idx_all = self._roi_targets_lists(proposals, targets, n_pos_max, n_tot)
         B = len(proposals)
         x = self.roi_align(feats[:4], self.STRIDES[:4], rois_b, 7)
         cls, reg = self.bbox_head(x.to(feats[0].dtype))
         loss_cls = F.cross_entropy(cls.float(), labels_c)
         pos_sel = torch.cat([torch.arange(n_pos_max, device=rois_b.device) + b * n_tot for b in range(B)])
-        pv = torch.cat(pos_valid_all).float()
         pl = labels_c[pos_sel].clamp(max=self.num_classes - 1)
         ar = torch.arange(pos_sel.numel(), device=reg.device)
         reg_p = reg.float()[pos_sel].view(-1, self.num_classes, 4)[ar, pl]
-        loss_bbox = ((reg_p - torch.cat(reg_t)).abs().sum(1) * pv).sum() / (B * n_tot)
+        loss_bbox = ((reg_p - reg_t).abs().sum(1) * pv).sum() / (B * n_tot)
         if padded and targets.masks is None:                                                      # Faster R-CNN: no mask branch
             return loss_cls, loss_bbox, None
         # masks on the positive RoIs (the first n_pos_max of every image)
@@ -683,20 +828,23 @@ class MiniMaskRCNN(nn.Module):
         logits = self.mask_head(xm.to(feats[0].dtype)).float()                                    # [B * P, classes, 28, 28]
         logit_c = logits[ar, pl]
         with torch.no_grad():
-            mt = []
             ms = cfg["mask_size"]
-            t = (torch.arange(ms, device=rois_b.device, dtype=torch.float32) + 0.5) / ms
-            H, W = img_hw
-            for b in range(B):
-                r = rois_b[b, :n_pos_max]
-                gx = (r[:, 0:1] + (r[:, 2:3] - r[:, 0:1]) * t[None]) / W * 2 - 1
-                gy = (r[:, 1:2] + (r[:, 3:4] - r[:, 1:2]) * t[None]) / H * 2 - 1
-                grid = torch.stack([gx[:, None, :].expand(-1, ms, ms), gy[:, :, None].expand(-1, ms, ms)], -1).reshape(1, -1, ms, 2)
-                gm = (targets.masks[b] if padded else targets[b]["masks"]).float()[None]          # [1, G, H, W]: all gt bitmaps as channels
-                smp = F.grid_sample(gm, grid, mode="bilinear", padding_mode="zeros", align_corners=False)   # [1, G, P * ms, ms]
-                smp = smp[0].view(gm.shape[1], n_pos_max, ms, ms)
-                mt.append((smp[gt_idx_all[b], torch.arange(n_pos_max, device=smp.device)] >= 0.5).float())
-            mt = torch.cat(mt)
+            if padded:                                                                            # once per batch: the assigned bitmap only
+                mt = self.mask_targets(targets.masks, rois_b[:, :n_pos_max], gt_idx, pos_valid, ms)
+            else:
+                mt = []
+                t = (torch.arange(ms, device=rois_b.device, dtype=torch.float32) + 0.5) / ms
+                H, W = img_hw
+                for b in range(B):
+                    r = rois_b[b, :n_pos_max]
+                    gx = (r[:, 0:1] + (r[:, 2:3] - r[:, 0:1]) * t[None]) / W * 2 - 1
+                    gy = (r[:, 1:2] + (r[:, 3:4] - r[:, 1:2]) * t[None]) / H * 2 - 1
+                    grid = torch.stack([gx[:, None, :].expand(-1, ms, ms), gy[:, :, None].expand(-1, ms, ms)], -1).reshape(1, -1, ms, 2)
+                    gm = targets[b]["masks"].float()[None]                                        # [1, G, H, W]: all gt bitmaps as channels
+                    smp = F.grid_sample(gm, grid, mode="bilinear", padding_mode="zeros", align_corners=False)   # [1, G, P * ms, ms]
+                    smp = smp[0].view(gm.shape[1], n_pos_max, ms, ms)
+                    mt.append((smp[gt_idx_all[b], torch.arange(n_pos_max, device=smp.device)] >= 0.5).float())
+                mt = torch.cat(mt)
         lm = F.binary_cross_entropy_with_logits(logit_c, mt, reduction="none").mean((1, 2))
         loss_mask = (lm * pv).sum() / pv.sum().clamp(min=1)
         return loss_cls, loss_bbox, loss_mask

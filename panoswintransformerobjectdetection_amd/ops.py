@@ -1576,6 +1576,110 @@ def max_iou_assign_batch(cand, gt, gt_count, pos_iou_thr, neg_iou_thr, min_pos_i
     return inds, miou
 
 
+def _sample_inputs(what, gt_inds, key):
+    if gt_inds.dim() != 2 or gt_inds.dtype != torch.int64 or tuple(key.shape) != tuple(gt_inds.shape) or key.device != gt_inds.device:
+        raise PswinError(f"{what}: gt_inds int64 [B, N] and key [B, N] on one device, got {tuple(gt_inds.shape)} {gt_inds.dtype} and "
+                         f"{tuple(key.shape)}")
+    return gt_inds.contiguous(), key.detach().float().contiguous()
+
+
+def sample_ranks(gt_inds, key, n_pos, n_neg):
+    """detector.sample_ranks on the GPU (pswin_sample_ranks): (pos_rank int64 [B, n_pos], neg_rank int64 [B, n_neg]) -- the first
+    candidates of the positive and of the negative order by (composed float32 key, index).  gt_inds int64 [B, N]; key f32 [B, N], finite
+    and >= 0.  A fixed number of launches for given (N, max(n_pos, n_neg)), no host synchronisation, no atomics: the call can be captured,
+    and a replay ranks whatever the buffers hold then.  The tree's partial lists live in one workspace per (B, N, k, device), written by
+    every call before it is read.  CPU tensors: the definition."""
+    if not gt_inds.is_cuda:
+        from . import detector
+        return detector.sample_ranks(gt_inds, key, n_pos, n_neg)
+    gt_inds, key = _sample_inputs("sample_ranks", gt_inds, key)
+    B, N = (int(v) for v in gt_inds.shape)
+    n_pos, n_neg = int(n_pos), int(n_neg)
+    k = max(n_pos, n_neg)
+    nbytes = int(_lib.load().pswin_sample_workspace(B, N, k))
+    _lib.check(min(nbytes, 0), "pswin_sample_workspace")
+    ws_key = ("sample_ws", B, N, k, _dev_key(gt_inds.device))
+    if ws_key not in _CACHE:
+        _CACHE[ws_key] = torch.empty(nbytes, dtype=torch.uint8, device=gt_inds.device)
+    pos_rank = torch.empty(B, n_pos, dtype=torch.int64, device=gt_inds.device)
+    neg_rank = torch.empty(B, n_neg, dtype=torch.int64, device=gt_inds.device)
+    call("pswin_sample_ranks", key, ptr(gt_inds), ptr(key), B, N, n_pos, n_neg, ptr(pos_rank), ptr(neg_rank), ptr(_CACHE[ws_key]))
+    return pos_rank, neg_rank
+
+
+def rpn_targets(gt_inds, key, anchors, gt, n_pos_max, n_tot):
+    """detector.rpn_targets on the GPU (pswin_sample_ranks, then one launch of pswin_rpn_targets): (idx int64 [B, n_pos_max + n_tot], valid
+    f32 of that shape, pos_valid bool [B, n_pos_max], reg_t f32 [B, n_pos_max, 4]).  gt_inds int64 [B, A]; key f32 [B, A]; anchors f32
+    [A, 4]; gt f32 [B, Gmax, 4].  Capturable as sample_ranks is.  CPU tensors: the definition."""
+    if not gt_inds.is_cuda:
+        from . import detector
+        return detector.rpn_targets(gt_inds, key, anchors, gt, n_pos_max, n_tot)
+    gt_inds, key = _sample_inputs("rpn_targets", gt_inds, key)
+    B, N = (int(v) for v in gt_inds.shape)
+    if tuple(anchors.shape) != (N, 4) or gt.dim() != 3 or gt.shape[0] != B or gt.shape[2] != 4 or anchors.device != key.device or gt.device != key.device:
+        raise PswinError(f"rpn_targets: anchors [{N}, 4] and gt [{B}, Gmax, 4] on the device of gt_inds, got {tuple(anchors.shape)} and {tuple(gt.shape)}")
+    n_pos_max, n_tot, Gmax, dev = int(n_pos_max), int(n_tot), int(gt.shape[1]), key.device
+    anchors, gt = anchors.detach().float().contiguous(), gt.detach().float().contiguous()
+    pos_rank, neg_rank = sample_ranks(gt_inds, key, n_pos_max, n_tot)
+    idx = torch.empty(B, n_pos_max + n_tot, dtype=torch.int64, device=dev)
+    valid = torch.empty(B, n_pos_max + n_tot, dtype=torch.float32, device=dev)
+    pos_valid = torch.empty(B, n_pos_max, dtype=torch.uint8, device=dev)
+    reg_t = torch.empty(B, n_pos_max, 4, dtype=torch.float32, device=dev)
+    call("pswin_rpn_targets", key, ptr(gt_inds), ptr(pos_rank), ptr(neg_rank), ptr(anchors), ptr(gt), B, N, Gmax, n_pos_max, n_tot, ptr(idx),
+         ptr(valid), ptr(pos_valid), ptr(reg_t))
+    return idx, valid, pos_valid.view(torch.bool), reg_t
+
+
+def roi_targets(gt_inds, key, cand, gt, gt_labels, num_classes, n_pos_max, n_tot, stds):
+    """detector.roi_targets on the GPU (pswin_sample_ranks, then one launch of pswin_roi_targets): (rois f32 [B, n_tot, 4], labels int64
+    [B, n_tot], reg_t f32 [B, n_pos_max, 4], pos_valid bool [B, n_pos_max], gt_idx int64 [B, n_pos_max]).  gt_inds int64 [B, N]; key f32
+    [B, N]; cand f32 [B, N, 4]; gt f32 [B, Gmax, 4]; gt_labels int64 [B, Gmax].  Capturable as sample_ranks is.  CPU tensors: the definition."""
+    if not gt_inds.is_cuda:
+        from . import detector
+        return detector.roi_targets(gt_inds, key, cand, gt, gt_labels, num_classes, n_pos_max, n_tot, stds)
+    gt_inds, key = _sample_inputs("roi_targets", gt_inds, key)
+    B, N = (int(v) for v in gt_inds.shape)
+    dev = key.device
+    if tuple(cand.shape) != (B, N, 4) or gt.dim() != 3 or gt.shape[0] != B or gt.shape[2] != 4 or tuple(gt_labels.shape) != tuple(gt.shape[:2]) or \
+            gt_labels.dtype != torch.int64 or any(t.device != dev for t in (cand, gt, gt_labels)):
+        raise PswinError(f"roi_targets: cand [{B}, {N}, 4], gt [{B}, Gmax, 4] and int64 gt_labels [{B}, Gmax] on the device of gt_inds, got "
+                         f"{tuple(cand.shape)}, {tuple(gt.shape)} and {tuple(gt_labels.shape)} {gt_labels.dtype}")
+    n_pos_max, n_tot, Gmax = int(n_pos_max), int(n_tot), int(gt.shape[1])
+    cand, gt, gt_labels = cand.detach().float().contiguous(), gt.detach().float().contiguous(), gt_labels.contiguous()
+    pos_rank, neg_order = sample_ranks(gt_inds, key, n_pos_max, n_tot)
+    rois = torch.empty(B, n_tot, 4, dtype=torch.float32, device=dev)
+    labels = torch.empty(B, n_tot, dtype=torch.int64, device=dev)
+    reg_t = torch.empty(B, n_pos_max, 4, dtype=torch.float32, device=dev)
+    pos_valid = torch.empty(B, n_pos_max, dtype=torch.uint8, device=dev)
+    gt_idx = torch.empty(B, n_pos_max, dtype=torch.int64, device=dev)
+    std4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    call("pswin_roi_targets", key, ptr(gt_inds), ptr(pos_rank), ptr(neg_order), ptr(cand), ptr(gt), ptr(gt_labels), B, N, Gmax, n_pos_max, n_tot,
+         int(num_classes), ctypes.cast(std4, ctypes.c_void_p), ptr(rois), ptr(labels), ptr(reg_t), ptr(pos_valid), ptr(gt_idx))
+    return rois, labels, reg_t, pos_valid.view(torch.bool), gt_idx
+
+
+def mask_targets(masks, rois, gt_idx, pos_valid, size=28):
+    """detector.mask_targets on the GPU in one launch (pswin_mask_targets): f32 [B P, size, size] of 0 / 1.  masks uint8 [B, Gmax, H, W];
+    rois f32 [B, P, 4]; gt_idx int64 [B, P]; pos_valid bool [B, P].  Reads at most four bytes of the one assigned bitmap per sample point
+    and nothing for a row whose pos_valid is false.  CPU tensors: the definition."""
+    if not masks.is_cuda:
+        from . import detector
+        return detector.mask_targets(masks, rois, gt_idx, pos_valid, size)
+    if masks.dim() != 4 or masks.dtype != torch.uint8 or rois.dim() != 3 or rois.shape[0] != masks.shape[0] or rois.shape[2] != 4 or \
+            tuple(gt_idx.shape) != tuple(rois.shape[:2]) or tuple(pos_valid.shape) != tuple(rois.shape[:2]) or gt_idx.dtype != torch.int64 or \
+            pos_valid.dtype not in (torch.bool, torch.uint8) or any(t.device != masks.device for t in (rois, gt_idx, pos_valid)):
+        raise PswinError(f"mask_targets: masks uint8 [B, Gmax, H, W], rois [B, P, 4], gt_idx int64 [B, P] and pos_valid bool [B, P] on one "
+                         f"device, got {tuple(masks.shape)} {masks.dtype}, {tuple(rois.shape)}, {tuple(gt_idx.shape)} {gt_idx.dtype}, "
+                         f"{tuple(pos_valid.shape)} {pos_valid.dtype}")
+    B, Gmax, H, W = (int(v) for v in masks.shape)
+    P, size = int(rois.shape[1]), int(size)
+    masks, rois, gt_idx = masks.contiguous(), rois.detach().float().contiguous(), gt_idx.contiguous()
+    pv = pos_valid.contiguous().view(torch.uint8)
+    out = torch.empty(B * P, size, size, dtype=torch.float32, device=masks.device)
+    call("pswin_mask_targets", rois, ptr(masks), ptr(rois), ptr(gt_idx), ptr(pv), B, P, Gmax, H, W, size, ptr(out), algo_bytes=B * P * size * size * 8)
+    return out
+
+
 def _lowp_or_f32(t):
     return t if t.dtype in (torch.float32, torch.bfloat16) else t.float()
 
