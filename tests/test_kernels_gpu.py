@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import panoswin_oracle as po
+from _attn_edge_cases import _attn_case, _attn_oracle, _fused_case, _fused_run
 from _util import golden
 from detfill import det_uniform
 
@@ -268,42 +269,6 @@ def test_pitch_static_resampling(ops, H, W):
     assert torch.allclose(xd.grad.cpu(), x.grad, rtol=1e-4, atol=1e-5)
 
 
-def _attn_case(n_rep, nW, heads, pano, mask_kind, seed):
-    C = heads * 32
-    n = n_rep * nW
-    x = det_uniform((n * 49, 3 * C), f"att:{seed}:qkv", 1.5)
-    alpha = det_uniform((169, heads), f"att:{seed}:a", 0.3)
-    beta = det_uniform((169, heads), f"att:{seed}:b", 0.3)
-    uv = torch.stack([det_uniform((nW, 49), f"att:{seed}:u", math.pi), det_uniform((nW, 49), f"att:{seed}:v", math.pi / 2)], -1)
-    uv[0, 45:] = 0.0
-    dist = po.haversine(uv, uv) if pano else None
-    mask = None
-    if mask_kind == 3:
-        mask = torch.where(det_uniform((nW, 49, 49), f"att:{seed}:m") > 0.4, torch.tensor(-100.0), torch.tensor(0.0))
-    elif mask_kind == 4:
-        mask = torch.where(det_uniform((n_rep, nW, 49, 49), f"att:{seed}:m4") > 0.4, torch.tensor(-100.0), torch.tensor(0.0))
-    gout = det_uniform((n * 49, C), f"att:{seed}:g", 1.0)
-    return x, alpha, beta, dist, mask, gout
-
-
-def _attn_oracle(x, alpha, beta, dist, mask, gout, heads, n_rep, nW):
-    C = heads * 32
-    x = x.clone().requires_grad_(True)
-    alpha, beta = alpha.clone().requires_grad_(True), beta.clone().requires_grad_(True)
-    idx = po.relative_position_index(7).reshape(-1)
-    b = beta[idx].reshape(49, 49, heads)
-    if dist is not None:
-        bias = dist[..., None] * alpha[idx].reshape(49, 49, heads)[None] + b
-        bias = bias.repeat(n_rep, 1, 1, 1)
-    else:
-        bias = b[None]
-    qkv = x.view(-1, 49, 3, C)
-    out = po.window_attention_core(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], 32 ** -0.5, bias.permute(0, 3, 1, 2), mask,
-                                   heads, 0.0, False).reshape(-1, C)
-    (out * gout).sum().backward()
-    return out.detach(), x.grad, alpha.grad, beta.grad
-
-
 @pytest.mark.parametrize("n_rep,nW,heads,pano,mask_kind,chunks", [
     (2, 3, 2, True, 0, None), (1, 5, 1, False, 0, None), (2, 3, 3, False, 3, None), (2, 3, 2, False, 4, None),
     (3, 4, 6, True, 3, None), (8, 15, 24, True, 0, None),
@@ -322,8 +287,8 @@ def test_window_attention_fwd_bwd(ops, n_rep, nW, heads, pano, mask_kind, chunks
     out = ops.window_attention(xd, ad, bd, None if dist is None else dist.to(DEV), maskd, heads, 32 ** -0.5, nb,
                                chunks=chunks)
     out.backward(gout.to(DEV).to(dtype))
-    # fp32: exact-f32 MFMA, differs from the oracle by summation order only.  bf16: bf16 operands (q*scale, P and
-    # dS are rounded to bf16), f32 accumulation.
+    # fp32: exact-f32 MFMA, differs from the oracle by summation order only.  bf16: bf16 operands (P and dS are rounded
+    # to bf16; q stays unscaled, the scale is folded into the exp2 argument), f32 accumulation.
     rt, at = (2e-5, 2e-5) if dtype == torch.float32 else (3e-2, 3e-2)
     assert torch.allclose(out.float().cpu(), ref_out, rtol=rt, atol=at)
     gs = ref_dx.abs().max().item()
@@ -726,54 +691,6 @@ def test_window_attention_module_against_the_reference_capture(ops, name, pano, 
 
 # ---- the per-window fused kernels: qkv -> attention -> proj (csrc/pswin_fused.hip, C = 96 / 3 heads) and qkv -> attention
 # (csrc/pswin_qkvattn.hip, C = 192 / 384), bf16 ------------------------------------------------------------------------------
-def _fused_case(B, nW, pano, mask_kind, seed, C=96):
-    from detfill import det_fill_module
-    att = po.WindowAttention(C, 7, C // 32)
-    det_fill_module(att, f"fz:{seed}")
-    with torch.no_grad():                       # the kernel's operands are bf16: the oracle sees the same rounded weights
-        for lin in (att.qkv, att.proj):
-            lin.weight.copy_(lin.weight.to(torch.bfloat16).float())
-    n = B * nW
-    x = det_uniform((n, 49, C), f"fz:{seed}:x", 1.0).to(torch.bfloat16).float()
-    uv = torch.stack([det_uniform((nW, 49), f"fz:{seed}:u", math.pi), det_uniform((nW, 49), f"fz:{seed}:v", math.pi / 2)], -1)
-    uv[0, 44:] = 0.0                            # zero-uv padding slots
-    mask = None
-    if mask_kind == 3:
-        mask = torch.where(det_uniform((nW, 49, 49), f"fz:{seed}:m") > 0.4, torch.tensor(-100.0), torch.tensor(0.0))
-    elif mask_kind == 4:
-        mask = torch.where(det_uniform((B, nW, 49, 49), f"fz:{seed}:m4") > 0.4, torch.tensor(-100.0), torch.tensor(0.0))
-    gout = det_uniform((n, 49, C), f"fz:{seed}:g", 1.0).to(torch.bfloat16).float()
-    return att, x, uv, mask, gout
-
-
-def _fused_run(ops, att_cpu, x, uv, mask, gout, B, nW, pano, mask_kind, fused, C=96):
-    """The product's WindowAttention chain on the GPU in bf16: the fused kernel (C = 96: with the proj Linear; C = 192 / 384: qkv +
-    attention core, then the proj GEMM) or the three-kernel chain."""
-    from panoswintransformerobjectdetection_amd.backbone import WindowAttention, _linear
-    heads = C // 32
-    att = WindowAttention(C, 7, heads)
-    att.load_state_dict(att_cpu.state_dict())
-    att = att.to(DEV)
-    xd = x.to(DEV).to(torch.bfloat16).view(-1, C).requires_grad_(True)
-    uvd = uv.to(DEV)
-    dist = ops.Tiles(ops.haversine_windows(uvd, uvd), symmetric=True) if pano else None
-    mt = None if mask is None else ops.Tiles(mask.reshape(-1, 49, 49).to(DEV))
-    nb = B * nW if mask_kind == 4 else nW
-    if fused and C == 96:
-        y = ops.window_attention_fused(xd, att, dist, mt, nb)
-    elif fused:
-        assert ops.window_attention_qkv_fused_supported(xd, heads)
-        y = _linear(ops.window_attention_qkv_fused(xd, att, dist, mt, nb), att.proj, torch.bfloat16, use_bias=False)
-    else:
-        qkv = _linear(xd, att.qkv, torch.bfloat16)
-        o = ops.window_attention(qkv, att.sphere_position_alpha_table_Te, att.sphere_position_beta_table_Te, dist, mt, heads,
-                                 att.scale, nb)
-        y = _linear(o, att.proj, torch.bfloat16, use_bias=False)
-    y.backward(gout.to(DEV).to(torch.bfloat16).view(-1, C))
-    grads = {k: p.grad.detach().float().cpu() for k, p in att.named_parameters() if p.grad is not None}
-    return y.detach().float().cpu(), xd.grad.float().cpu(), grads
-
-
 FUSED_CASES = [(2, 3, True, 0), (1, 5, False, 0), (3, 4, False, 3), (2, 3, False, 4), (2, 3, True, 3), (9, 2, True, 0),
                (8, 15, True, 0), (1, 1, True, 0)]
 
