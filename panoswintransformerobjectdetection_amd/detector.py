@@ -17,12 +17,13 @@ so nothing here is checked against reference outputs.  RoIAlign is the published
 of the definition in tests/); NMS is the greedy rule: on the GPU one HIP launch per image (nms_keep_groups -> pswin_nms_groups), on the CPU a fixed-point iteration (nms_keep).  The other
 head operators are ordinary PyTorch-ROCm operators (MIOpen / hipBLASLt, bf16 autocast).
 
-TARGETS: a list of dicts per image (shapes tied to one batch), or a PaddedTargets (fixed shapes, the box count of every image on the
-device: the form a captured step is replayed on with the next batch's annotations).  With a PaddedTargets both stages' MaxIoUAssigner
-run as HIP kernels for the whole batch (max_iou_assign_batch -> pswin_max_iou_assign), pinned to the reference's own results
-(tests/golden/max_iou_assign_batch.npz), and so does everything between "assigned" and "loss", once per batch: the RandomSampler with a
-defined tie order, the box targets and the mask targets (sample_ranks, rpn_targets, roi_targets, mask_targets below are the definitions;
-ops.rpn_targets / roi_targets / mask_targets -> csrc/pswin_targets.hip).
+TARGETS: a PaddedTargets (fixed shapes, the box count of every image on the device: the form a captured step is replayed on with the
+next batch's annotations), or a list of dicts per image, which heads_loss pads on entry (PaddedTargets.of; shapes tied to that batch).
+There is one target path for both: each stage's MaxIoUAssigner for the whole batch (max_iou_assign_batch, pinned to the reference's own
+results: tests/golden/max_iou_assign_batch.npz), then everything between "assigned" and "loss" once per batch -- the RandomSampler, the
+box targets and the mask targets (sample_ranks, rpn_targets, roi_targets, mask_targets below).  On the CPU these definitions run; on the
+GPU the HIP kernels pinned to them (ops.max_iou_assign_batch -> pswin_max_iou_assign; ops.rpn_targets / roi_targets / mask_targets ->
+csrc/pswin_targets.hip), and a missing kernel is an error.  The sampler's tie rule is stated once, at sample_ranks.
 
 INFERENCE: `heads_predict` / `simple_test` (TwoStageDetector.simple_test, mmdet/models/detectors/two_stage.py:217) return a Detections:
 fixed shapes, the detection count of every image on the device, no host synchronisation -- one captured graph serves every batch.  The
@@ -96,11 +97,12 @@ def max_iou_assign(bboxes, gt_bboxes, pos_iou_thr, neg_iou_thr, min_pos_iou=0.0,
 _CONSTS = {}
 
 
-def _const(values, like):
-    """A small constant tensor on `like`'s device, built once (a host-to-device copy per call would also break hipGraph capture)."""
-    key = (tuple(float(v) for v in values), str(like.device), like.dtype)
+def _const(values, like, dtype=None):
+    """A small constant tensor on `like`'s device (of its dtype unless one is given), built once: a host-to-device copy per call would
+    also break hipGraph capture.  Shared by its callers: read it, never write it."""
+    key = (tuple(float(v) for v in values), str(like.device), dtype or like.dtype)
     if key not in _CONSTS:
-        _CONSTS[key] = torch.tensor(key[0], device=like.device, dtype=like.dtype)
+        _CONSTS[key] = torch.tensor(key[0], device=like.device, dtype=key[2])
     return _CONSTS[key]
 
 
@@ -312,6 +314,26 @@ class PaddedTargets:
 
     def __init__(self, boxes, labels, count, masks=None):
         self.boxes, self.labels, self.count, self.masks = boxes, labels, count, masks
+        self.list_counts = None                      # of(lists): the host's copy of the counts, by which the RoI stage lays out its keys
+
+    @classmethod
+    def of(cls, targets):
+        """`targets` itself if it is a PaddedTargets; a list of dicts per image (boxes [G, 4], labels [G], masks [G, H, W] or none), padded
+        with zeros to Gmax = max(1, the largest count).  Device operations of host-known shapes only, and `count` is a cached constant
+        (_const: read it, never copy_from into it), so that a captured step may take lists: its warm-up passes fill the cache."""
+        if isinstance(targets, cls):
+            return targets
+        counts = tuple(int(t["boxes"].shape[0]) for t in targets)
+        B, Gmax, ref = len(counts), max(1, *counts), targets[0]["boxes"]
+        out = cls(ref.new_zeros(B, Gmax, 4, dtype=torch.float32), ref.new_zeros(B, Gmax, dtype=torch.long), _const(counts, ref, torch.int32))
+        if "masks" in targets[0]:
+            out.masks = ref.new_zeros(B, Gmax, *targets[0]["masks"].shape[1:], dtype=torch.uint8)
+        for b, (t, n) in enumerate(zip(targets, counts)):
+            out.boxes[b, :n], out.labels[b, :n] = t["boxes"], t["labels"]
+            if out.masks is not None:
+                out.masks[b, :n] = t["masks"].to(torch.uint8)
+        out.list_counts = counts
+        return out
 
     @classmethod
     def allocate(cls, B, max_gt, device, mask_hw=None):
@@ -642,10 +664,10 @@ class MiniMaskRCNN(nn.Module):
     STRIDES = (4, 8, 16, 32, 64)
     rand_like = staticmethod(torch.rand_like)    # the samplers' random keys (tests substitute a fixed sequence to compare eager and replayed steps)
     roi_align = staticmethod(roi_align)          # the HIP operator; tests of the head stand-ins on the CPU substitute the PyTorch statement
-    assign = staticmethod(max_iou_assign_batch)  # the target assigner of a PaddedTargets batch (both stages, once per batch each)
-    rpn_targets = staticmethod(rpn_targets_dispatch)      # PaddedTargets: the RPN's sampler and box targets, once per batch
-    roi_targets = staticmethod(roi_targets_dispatch)      # PaddedTargets: the RoI head's sampler, RoIs, labels and box targets, once per batch
-    mask_targets = staticmethod(mask_targets_dispatch)    # PaddedTargets: the mask head's targets, once per batch
+    assign = staticmethod(max_iou_assign_batch)  # the target assigner of a batch (both stages, once per batch each)
+    rpn_targets = staticmethod(rpn_targets_dispatch)      # the RPN's sampler and box targets, once per batch
+    roi_targets = staticmethod(roi_targets_dispatch)      # the RoI head's sampler, RoIs, labels and box targets, once per batch
+    mask_targets = staticmethod(mask_targets_dispatch)    # the mask head's targets, once per batch
     multiclass_nms = staticmethod(multiclass_nms_batch)   # test time: softmax, decode, class-wise NMS, top K of a batch
     paste = staticmethod(paste_masks_dispatch)            # test time: the detections' masks pasted into the image
     BBOX_STDS = (0.1, 0.1, 0.2, 0.2)
@@ -716,103 +738,47 @@ class MiniMaskRCNN(nn.Module):
         cls_all, reg_all = self._rpn_flatten(rpn_outs)
         loss_cls = loss_reg = cls_all.new_zeros(())
         n_pos_max, n_tot = int(cfg["num"] * cfg["pos_fraction"]), cfg["num"]
-        proposals = []
-        padded = isinstance(targets, PaddedTargets)
-        if padded:                                                                                # the anchors are shared by the images
-            inds_all = self.assign(flat_a, targets.boxes, targets.count, cfg["pos"], cfg["neg"], cfg["min_pos"], True)[0]
-            # assign, sample and encode once per batch (rpn_targets); the keys are drawn per image, as the list form draws them
-            proto = cls_all.new_empty(flat_a.shape[0])
-            key = torch.stack([self.rand_like(proto) for _ in range(B)])
-            idx, valid, pos_valid, d_t = self.rpn_targets(inds_all, key, flat_a, targets.boxes, n_pos_max, n_tot)
-            tgt = torch.cat([torch.ones(n_pos_max, device=key.device), torch.zeros(n_tot, device=key.device)])
-            avg = valid.sum(1).clamp(min=1)                                                       # [B]
-            bce = F.binary_cross_entropy_with_logits(cls_all.gather(1, idx), tgt[None].expand(B, -1), reduction="none")
-            l_cls = (bce * valid).sum(1) / avg
-            reg_p = reg_all.gather(1, idx[:, :n_pos_max, None].expand(-1, -1, 4))
-            l_reg = ((reg_p - d_t).abs().sum(2) * pos_valid.float()).sum(1) / avg
-            for b in range(B):                                                                    # per image, then over the batch in image order
-                loss_cls, loss_reg = loss_cls + l_cls[b], loss_reg + l_reg[b]
-                with torch.no_grad():
-                    proposals.append(self._proposals(cls_all[b], reg_all[b], anchors, cfg, img_hw)[0])
-            return loss_cls / B, loss_reg / B, proposals
-        for b in range(B):
-            # MaxIoUAssigner(pos 0.7, neg 0.3, min_pos 0.3, match_low_quality) -- configs/_base_/models/mask_rcnn_swin_fpn.py:79-85
-            gt = targets[b]["boxes"]
-            gt_inds = max_iou_assign(flat_a, gt, cfg["pos"], cfg["neg"], cfg["min_pos"], True)
-            label = gt_inds.clamp(max=1).to(flat_a.dtype)                                         # 1 positive, 0 negative, -1 neither
-            arg = (gt_inds - 1).clamp(min=0)
-            best = label
-            # random sampling with static shapes: rank by a random key, positives first
-            key = self.rand_like(best)
-            behind = key + 2
-            pos_rank = torch.argsort(torch.where(label == 1, key, behind))[:n_pos_max]
-            pos_valid = label[pos_rank] == 1
-            neg_rank = torch.argsort(torch.where(label == 0, key, behind))[:n_tot]
-            n_pos = pos_valid.sum()
-            neg_valid = (label[neg_rank] == 0) & (torch.arange(n_tot, device=key.device) < (n_tot - n_pos))
-            idx = torch.cat([pos_rank, neg_rank])
-            valid = torch.cat([pos_valid, neg_valid]).float()
-            tgt = torch.cat([torch.ones_like(pos_valid, dtype=torch.float32), torch.zeros(n_tot, device=key.device)])
-            avg = valid.sum().clamp(min=1)
-            loss_cls = loss_cls + (F.binary_cross_entropy_with_logits(cls_all[b, idx], tgt, reduction="none") * valid).sum() / avg
-            d_t = encode_deltas(flat_a[pos_rank], gt[arg[pos_rank]], (1.0, 1.0, 1.0, 1.0))
-            loss_reg = loss_reg + ((reg_all[b, pos_rank] - d_t).abs().sum(1) * pos_valid.float()).sum() / avg
+        targets, proposals = PaddedTargets.of(targets), []
+        # MaxIoUAssigner(pos 0.7, neg 0.3, min_pos 0.3, match_low_quality) -- configs/_base_/models/mask_rcnn_swin_fpn.py:79-85; the anchors
+        # are shared by the images
+        inds_all = self.assign(flat_a, targets.boxes, targets.count, cfg["pos"], cfg["neg"], cfg["min_pos"], True)[0]
+        # assign, sample and encode once per batch (rpn_targets); one key vector per image, drawn in image order
+        proto = cls_all.new_empty(flat_a.shape[0])
+        key = torch.stack([self.rand_like(proto) for _ in range(B)])
+        idx, valid, pos_valid, d_t = self.rpn_targets(inds_all, key, flat_a, targets.boxes, n_pos_max, n_tot)
+        tgt = torch.cat([torch.ones(n_pos_max, device=key.device), torch.zeros(n_tot, device=key.device)])
+        avg = valid.sum(1).clamp(min=1)                                                           # [B]
+        bce = F.binary_cross_entropy_with_logits(cls_all.gather(1, idx), tgt[None].expand(B, -1), reduction="none")
+        l_cls = (bce * valid).sum(1) / avg
+        reg_p = reg_all.gather(1, idx[:, :n_pos_max, None].expand(-1, -1, 4))
+        l_reg = ((reg_p - d_t).abs().sum(2) * pos_valid.float()).sum(1) / avg
+        for b in range(B):                                                                        # per image, then over the batch in image order
+            loss_cls, loss_reg = loss_cls + l_cls[b], loss_reg + l_reg[b]
             with torch.no_grad():
                 proposals.append(self._proposals(cls_all[b], reg_all[b], anchors, cfg, img_hw)[0])
         return loss_cls / B, loss_reg / B, proposals
 
     # -- RoI heads ------------------------------------------------------------------------------------------------------
-    def _roi_targets_lists(self, proposals, targets, n_pos_max, n_tot):
-        """The RoI head's sampler and targets for the list form of the targets, image by image: (rois [B, n_tot, 4], labels [B * n_tot],
-        reg_t [B * n_pos_max, 4], pos_valid as f32 [B * n_pos_max], per image gt_idx [n_pos_max])"""
-        cfg = self.rcnn_cfg
-        rois, labels, reg_t, pos_valid_all, gt_idx_all = [], [], [], [], []
-        for b, props in enumerate(proposals):
-            # MaxIoUAssigner(pos 0.5, neg 0.5, min_pos 0.5, match_low_quality=True) -- mask_rcnn_swin_fpn.py:101-107
-            gt, gl = targets[b]["boxes"], targets[b]["labels"]
-            cand = torch.cat([gt, props], 0)                                                      # add_gt_as_proposals
-            gt_inds = max_iou_assign(cand, gt, cfg["pos"], cfg["pos"], cfg["pos"], True)
-            is_pos, arg = gt_inds > 0, (gt_inds - 1).clamp(min=0)
-            best = is_pos.float()
-            key = self.rand_like(best)
-            behind = key + 2
-            pos_rank = torch.argsort(torch.where(is_pos, key, behind))[:n_pos_max]
-            pos_valid = is_pos[pos_rank]
-            # the positive slots that found no positive were filled with the lowest-key non-positives (they count as background
-            # below): the negatives proper are the NEXT ones in that order, so that no RoI is sampled twice
-            filler = n_pos_max - pos_valid.sum()
-            neg_order = torch.argsort(torch.where(~is_pos, key, behind))
-            take = (torch.arange(n_tot - n_pos_max, device=key.device) + filler).clamp(max=neg_order.numel() - 1)
-            neg_rank = neg_order[take]
-            idx = torch.cat([pos_rank, neg_rank])
-            rois.append(cand[idx])
-            lab = torch.where(torch.cat([pos_valid, torch.zeros_like(neg_rank, dtype=torch.bool)]), gl[arg[idx]],
-                              torch.full_like(idx, self.num_classes))                              # background = num_classes
-            labels.append(lab)
-            reg_t.append(encode_deltas(cand[pos_rank], gt[arg[pos_rank]], (0.1, 0.1, 0.2, 0.2)))
-            pos_valid_all.append(pos_valid)
-            gt_idx_all.append(arg[pos_rank])
-        return torch.stack(rois), torch.cat(labels), torch.cat(reg_t), torch.cat(pos_valid_all).float(), gt_idx_all
-
     def _roi_losses(self, feats, proposals, targets, img_hw):
         cfg = self.rcnn_cfg
         n_tot, n_pos_max = cfg["num"], int(cfg["num"] * cfg["pos_fraction"])
-        padded = isinstance(targets, PaddedTargets)
+        targets = PaddedTargets.of(targets)
+        B, Gmax, R = len(proposals), targets.max_gt, proposals[0].shape[0]
         with torch.no_grad():
-            if padded:                                                                            # add_gt_as_proposals: the padded gt rows lead
-                cand_all = torch.cat([targets.boxes, torch.stack(proposals)], 1)
-                inds_all = self.assign(cand_all, targets.boxes, targets.count, cfg["pos"], cfg["pos"], cfg["pos"], True,
-                                       lead_gt=targets.max_gt)[0]
-                # the negatives are gt_inds == 0, and the ignored rows (the gt padding) sort behind everything in both orders, so that a
-                # padding row is never drawn as a RoI or as a background filler (sample_ranks); once per batch, the keys drawn per image
-                proto = cand_all.new_empty(cand_all.shape[1])
-                key = torch.stack([self.rand_like(proto) for _ in proposals])
-                rois_b, labels_b, reg_t, pos_valid, gt_idx = self.roi_targets(inds_all, key, cand_all, targets.boxes, targets.labels,
-                                                                              self.num_classes, n_pos_max, n_tot, (0.1, 0.1, 0.2, 0.2))
-                labels_c, reg_t, pv = labels_b.reshape(-1), reg_t.reshape(-1, 4), pos_valid.reshape(-1).float()
-            else:
-                rois_b, labels_c, reg_t, pv, gt_idx_all = self._roi_targets_lists(proposals, targets, n_pos_max, n_tot)
-        B = len(proposals)
+            # MaxIoUAssigner(pos 0.5, neg 0.5, min_pos 0.5, match_low_quality=True) -- mask_rcnn_swin_fpn.py:101-107; add_gt_as_proposals:
+            # the padded gt rows lead
+            cand_all = torch.cat([targets.boxes, torch.stack(proposals)], 1)
+            inds_all = self.assign(cand_all, targets.boxes, targets.count, cfg["pos"], cfg["pos"], cfg["pos"], True, lead_gt=Gmax)[0]
+            # the negatives are gt_inds == 0, and the ignored rows (the gt padding) sort behind everything in both orders, so that a
+            # padding row is never drawn as a RoI or as a background filler (sample_ranks); once per batch.  One key vector per image, drawn
+            # in image order: Gmax + R keys, or for padded lists the G_b + R keys of the image's own rows (the padding's key stays 0)
+            def keys(n):
+                k = self.rand_like(cand_all.new_empty(n + R))
+                return k if n == Gmax else torch.cat([k[:n], k.new_zeros(Gmax - n), k[n:]])
+            key = torch.stack([keys(n) for n in targets.list_counts or [Gmax] * B])
+            rois_b, labels_b, reg_t, pos_valid, gt_idx = self.roi_targets(inds_all, key, cand_all, targets.boxes, targets.labels,
+                                                                          self.num_classes, n_pos_max, n_tot, (0.1, 0.1, 0.2, 0.2))
+            labels_c, reg_t, pv = labels_b.reshape(-1), reg_t.reshape(-1, 4), pos_valid.reshape(-1).float()
         x = self.roi_align(feats[:4], self.STRIDES[:4], rois_b, 7)
         cls, reg = self.bbox_head(x.to(feats[0].dtype))
         loss_cls = F.cross_entropy(cls.float(), labels_c)
@@ -821,38 +787,24 @@ class MiniMaskRCNN(nn.Module):
         ar = torch.arange(pos_sel.numel(), device=reg.device)
         reg_p = reg.float()[pos_sel].view(-1, self.num_classes, 4)[ar, pl]
         loss_bbox = ((reg_p - reg_t).abs().sum(1) * pv).sum() / (B * n_tot)
-        if padded and targets.masks is None:                                                      # Faster R-CNN: no mask branch
+        if targets.masks is None:                                                                 # Faster R-CNN: no mask branch
             return loss_cls, loss_bbox, None
         # masks on the positive RoIs (the first n_pos_max of every image)
         xm = self.roi_align(feats[:4], self.STRIDES[:4], rois_b[:, :n_pos_max], 14)
         logits = self.mask_head(xm.to(feats[0].dtype)).float()                                    # [B * P, classes, 28, 28]
         logit_c = logits[ar, pl]
-        with torch.no_grad():
-            ms = cfg["mask_size"]
-            if padded:                                                                            # once per batch: the assigned bitmap only
-                mt = self.mask_targets(targets.masks, rois_b[:, :n_pos_max], gt_idx, pos_valid, ms)
-            else:
-                mt = []
-                t = (torch.arange(ms, device=rois_b.device, dtype=torch.float32) + 0.5) / ms
-                H, W = img_hw
-                for b in range(B):
-                    r = rois_b[b, :n_pos_max]
-                    gx = (r[:, 0:1] + (r[:, 2:3] - r[:, 0:1]) * t[None]) / W * 2 - 1
-                    gy = (r[:, 1:2] + (r[:, 3:4] - r[:, 1:2]) * t[None]) / H * 2 - 1
-                    grid = torch.stack([gx[:, None, :].expand(-1, ms, ms), gy[:, :, None].expand(-1, ms, ms)], -1).reshape(1, -1, ms, 2)
-                    gm = targets[b]["masks"].float()[None]                                        # [1, G, H, W]: all gt bitmaps as channels
-                    smp = F.grid_sample(gm, grid, mode="bilinear", padding_mode="zeros", align_corners=False)   # [1, G, P * ms, ms]
-                    smp = smp[0].view(gm.shape[1], n_pos_max, ms, ms)
-                    mt.append((smp[gt_idx_all[b], torch.arange(n_pos_max, device=smp.device)] >= 0.5).float())
-                mt = torch.cat(mt)
+        with torch.no_grad():                                                                     # once per batch: the assigned bitmap only
+            mt = self.mask_targets(targets.masks, rois_b[:, :n_pos_max], gt_idx, pos_valid, cfg["mask_size"])
         lm = F.binary_cross_entropy_with_logits(logit_c, mt, reduction="none").mean((1, 2))
         loss_mask = (lm * pv).sum() / pv.sum().clamp(min=1)
         return loss_cls, loss_bbox, loss_mask
 
     def heads_loss(self, feats, targets, img_hw):
-        """Everything behind the backbone: dict of the 5 Mask R-CNN losses (two_stage.py:116-175).  targets: a list of dicts (boxes,
-        labels, masks) per image, or a PaddedTargets -- fixed shapes whatever the images' box counts, the form a captured step can be
-        replayed on; without masks it is the Faster R-CNN step (4 losses)."""
+        """Everything behind the backbone: dict of the 5 Mask R-CNN losses (two_stage.py:116-175).  targets: a PaddedTargets -- fixed shapes
+        whatever the images' box counts, the form a captured step can be replayed on -- or a list of dicts (boxes, labels, masks) per image,
+        which is padded here (PaddedTargets.of) and from then on IS one: both forms run the same assigner, sampler and target code.  Without
+        masks it is the Faster R-CNN step (4 losses).  An image without boxes has only negative candidates, in either form."""
+        targets = PaddedTargets.of(targets)
         if self.channels_last:
             feats = [f.contiguous(memory_format=torch.channels_last) for f in feats]
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):

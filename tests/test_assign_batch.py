@@ -16,6 +16,7 @@ import _roi_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GMAX = 16
+LIST_FORM_RTOL = 1e-6
 
 
 @pytest.fixture(scope="module")
@@ -213,3 +214,28 @@ def test_heads_loss_with_padding_never_samples_a_padding_row(heads, masks):
         else:
             assert p.grad is not None and torch.isfinite(p.grad).all(), k
     assert all(f.grad is not None and torch.isfinite(f.grad).all() for f in fs)
+
+
+def test_list_targets_give_what_the_list_form_gave_before_it_was_padded_on_entry(heads):
+    """Lists with ragged counts (3, 7) through both target stages against tests/golden/heads_list_form.npz, recorded by
+    tools/gen_heads_list_golden.py on the last commit whose list form had a sampler, a box encoding and a mask sampling of its own.  The
+    keys are all distinct (tests/_heads_list_case.py), so no outcome depends on a tie.  The RoIs handed to roi_align are copies of
+    candidate rows: bit-equal.  The losses pass through float32 Linear layers and convolutions whose summation order belongs to the CPU
+    and its BLAS.  Measured spread: on the recording machine that commit twice, and this code, give all five losses bit for bit; the
+    same commit on a second machine (another CPU) gives four of them bit for bit and loss_cls 420.660187 against 420.660217, 7.25e-8
+    relative (one float32 ulp), and this code gives there what that commit gives there.  LIST_FORM_RTOL = 1e-6 is 14 times that spread,
+    8 float32 epsilons."""
+    import _heads_list_case as case
+    m, _, _ = heads
+    gold = dict(np.load(os.path.join(ROOT, "tests", "golden", "heads_list_form.npz")))
+    assert tuple(gold["counts"]) == case.COUNTS
+    assert gold["seeds"].tolist() == [case.SEED_RPN, case.SEED_FPN, case.SEED_PROPOSALS, case.SEED_KEYS]
+    rpn_outs, fpn, proposals = case.inputs()
+    assert torch.equal(torch.stack(proposals), torch.from_numpy(gold["proposals"]))
+    got = case.run(m, case.targets(), rpn_outs, fpn, proposals)
+    for k in ("rois_box", "rois_mask"):
+        assert torch.equal(got[k], torch.from_numpy(gold[k])), k
+    for k in ("loss_rpn_cls", "loss_rpn_bbox", "loss_cls", "loss_bbox", "loss_mask"):
+        rel = abs(float(got[k]) - float(gold[k])) / abs(float(gold[k]))
+        print(f"{k}: got {float(got[k]):.9g} recorded {float(gold[k]):.9g} relative difference {rel:.3g}")
+        assert rel <= LIST_FORM_RTOL, (k, float(got[k]), float(gold[k]))
