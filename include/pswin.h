@@ -860,6 +860,35 @@ int pswin_roi_targets(const long long* gt_inds, const long long* pos_rank, const
 int pswin_mask_targets(const unsigned char* masks, const float* rois, const long long* gt_idx, const unsigned char* pos_valid, int B, int P,
                        int Gmax, int H, int W, int size, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The RPN's proposals of a batch (csrc/pswin_proposals.hip; panoswintransformerobjectdetection_amd/detector.py:
+ * proposals_batch, the stacked MiniMaskRCNN._proposals)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* RPNHead.get_bboxes for a whole batch (detector.proposals_batch):
+ *   scores f32 [B][A] raw logits of either sign, deltas f32 [B][A][4], anchors f32 [A][4] shared by the images; the A anchors are the L
+ *   pyramid levels one after the other, level_sizes: HOST array of their L sizes n_l.
+ *   Per (image, level): the first k_l = min(nms_pre, n_l) candidates in descending score, equal scores (+0.0 and -0.0 are equal) in
+ *   ascending anchor index; decoded as detector.decode_deltas(anchor, delta, stds 1, (img_h, img_w)) in float32 operation by operation
+ *   (only expf may differ from the host); the greedy rule of pswin_nms_groups on all B L lists in one call.  Per image the candidates of
+ *   all levels are concatenated level-major in rank order, a suppressed one's score becomes -1e4, and the first
+ *   P = min(max_per_img, sum_l k_l) in descending score, equal scores in ascending concatenated position, are the result:
+ *   rois f32 [B][P][4], out_scores f32 [B][P], count int32 [B] (the rows whose score is > -1e4: the survivors, which lead).
+ * The orders are those of 64-bit values (order bits of the score) << 32 | index, unique per candidate, taken through reduction trees of
+ * LDS sorts over chunks of pswin_rpn_proposals_rows_per_workgroup() candidates: the result does not depend on the order of execution.  No
+ * atomics, no host synchronisation, nothing to clear between calls: everything the call reads from the workspace it has written before.
+ * pswin_rpn_proposals_launches(level_sizes, L, nms_pre, max_per_img) kernel launches, whatever B.  NaN scores and scores <= -1e4 leave the
+ * order unspecified, but every index used lies in range.
+ * Limits: 1 <= L <= 8, n_l >= 1, 1 <= nms_pre <= 2048, max_per_img >= 1 and P <= 2048, B L <= 2048, B A < 2^31; 16-byte aligned deltas /
+ * anchors / rois and workspace of pswin_rpn_proposals_workspace(level_sizes, L, B, nms_pre, max_per_img) bytes (PSWIN_ERR_ARG beyond
+ * the limits or 2^31 - 1 bytes); anything else is PSWIN_ERR_ARG. */
+int pswin_rpn_proposals_rows_per_workgroup(void);                /* candidates one workgroup sorts (the chunk of the trees) */
+int pswin_rpn_proposals_launches(const int* level_sizes, int L, int nms_pre, int max_per_img);
+int pswin_rpn_proposals_workspace(const int* level_sizes, int L, int B, int nms_pre, int max_per_img);
+int pswin_rpn_proposals(const float* scores, const float* deltas, const float* anchors, const int* level_sizes, int L, int B, int nms_pre,
+                        float iou_thr, int max_per_img, int img_h, int img_w, float* rois, float* out_scores, int32_t* count, void* workspace,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,10 @@ _PROTOTYPES = {
     "pswin_rpn_targets": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pswin_roi_targets": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pswin_mask_targets": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "pswin_rpn_proposals_rows_per_workgroup": [],
+    "pswin_rpn_proposals_launches": [_vp, _i, _i, _i],
+    "pswin_rpn_proposals_workspace": [_vp, _i, _i, _i, _i],
+    "pswin_rpn_proposals": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pswin_gemm_nt_supported": [ctypes.c_longlong, _i, _i],
     "pswin_gemm_nt": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],
     "pswin_gemm_nt_f32": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],

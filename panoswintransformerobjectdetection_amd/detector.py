@@ -14,7 +14,10 @@ the reference's configuration numbers (configs/_base_/models/mask_rcnn_swin_fpn.
 PARITY: unpinned.  The reference tree does not contain mmcv.ops (RoIAlign, NMS CUDA sources) nor a fixture for any head,
 so nothing here is checked against reference outputs.  RoIAlign is the published operator with the config's sampling_ratio = 0
 (adaptive grid) as hand-written HIP kernels, forward and backward (csrc/pswin_roi.hip, checked against a plain PyTorch statement
-of the definition in tests/); NMS is the greedy rule: on the GPU one HIP launch per image (nms_keep_groups -> pswin_nms_groups), on the CPU a fixed-point iteration (nms_keep).  The other
+of the definition in tests/); NMS is the greedy rule: on the CPU a fixed-point iteration (nms_keep), on the GPU pswin_nms_groups.  The
+proposal stage (per level top nms_pre, decode, NMS, top max_per_img: proposals_batch, the stacked _proposals) runs on the GPU once per
+batch as HIP kernels whose launch count does not depend on the batch size (ops.rpn_proposals -> csrc/pswin_proposals.hip, all images'
+levels in one pswin_nms_groups call); beyond the kernels' limits the definition runs on the device image by image.  The other
 head operators are ordinary PyTorch-ROCm operators (MIOpen / hipBLASLt, bf16 autocast).
 
 TARGETS: a PaddedTargets (fixed shapes, the box count of every image on the device: the form a captured step is replayed on with the
@@ -287,6 +290,30 @@ def rpn_targets_dispatch(gt_inds, key, anchors, gt, n_pos_max, n_tot):
         from . import ops
         return ops.rpn_targets(gt_inds, key, anchors, gt, n_pos_max, n_tot)
     return rpn_targets(gt_inds, key, anchors, gt, n_pos_max, n_tot)
+
+
+def proposals_batch(cls_all, reg_all, anchors, cfg, img_hw):
+    """The RPN's proposals of a batch (the definition of ops.rpn_proposals): MiniMaskRCNN._proposals image by image, stacked.  cls_all f32
+    [B, A] raw logits and reg_all f32 [B, A, 4] as _rpn_flatten returns them, anchors: the per-level list of make_anchors, cfg: nms_pre,
+    nms, max_per_img -> (rois f32 [B, P, 4], scores f32 [B, P], count int32 [B]) with P = min(max_per_img, sum over the levels of
+    min(nms_pre, n_l)).  ALL P rows are defined, not only the survivors (the training path hands the suppressed tail to the RoI assigner
+    as candidates too): count[b] is the number of rows whose score is > -1e4, the survivors of the NMS, and they lead; the suppressed
+    candidates follow in the order of the concatenated levels."""
+    with torch.no_grad():
+        props = [MiniMaskRCNN._proposals(cls_all[b], reg_all[b], anchors, cfg, img_hw) for b in range(cls_all.shape[0])]
+    scores = torch.stack([p[1] for p in props])
+    return torch.stack([p[0] for p in props]), scores, (scores > -1e4).sum(1).to(torch.int32)
+
+
+def proposals_batch_dispatch(cls_all, reg_all, anchors, cfg, img_hw):
+    """proposals_batch.  On the GPU inside the kernels' limits (ops.rpn_proposals_supported): HIP kernels for the whole batch, a number
+    of launches that does not depend on B (ops.rpn_proposals -> pswin_rpn_proposals); outside the limits the definition on the device,
+    image by image, as nms_keep_groups falls back for lists above 2048; on the CPU the definition."""
+    if cls_all.is_cuda:
+        from . import ops
+        if ops.rpn_proposals_supported([a.shape[0] for a in anchors], cls_all.shape[0], cfg["nms_pre"], cfg["max_per_img"]):
+            return ops.rpn_proposals(cls_all, reg_all, anchors, cfg["nms_pre"], cfg["nms"], cfg["max_per_img"], img_hw)
+    return proposals_batch(cls_all, reg_all, anchors, cfg, img_hw)
 
 
 def roi_targets_dispatch(gt_inds, key, cand, gt, gt_labels, num_classes, n_pos_max, n_tot, stds):
@@ -668,6 +695,7 @@ class MiniMaskRCNN(nn.Module):
     rpn_targets = staticmethod(rpn_targets_dispatch)      # the RPN's sampler and box targets, once per batch
     roi_targets = staticmethod(roi_targets_dispatch)      # the RoI head's sampler, RoIs, labels and box targets, once per batch
     mask_targets = staticmethod(mask_targets_dispatch)    # the mask head's targets, once per batch
+    proposals = staticmethod(proposals_batch_dispatch)    # the RPN's proposals (top nms_pre, decode, NMS, top max_per_img), once per batch
     multiclass_nms = staticmethod(multiclass_nms_batch)   # test time: softmax, decode, class-wise NMS, top K of a batch
     paste = staticmethod(paste_masks_dispatch)            # test time: the detections' masks pasted into the image
     BBOX_STDS = (0.1, 0.1, 0.2, 0.2)
@@ -738,7 +766,7 @@ class MiniMaskRCNN(nn.Module):
         cls_all, reg_all = self._rpn_flatten(rpn_outs)
         loss_cls = loss_reg = cls_all.new_zeros(())
         n_pos_max, n_tot = int(cfg["num"] * cfg["pos_fraction"]), cfg["num"]
-        targets, proposals = PaddedTargets.of(targets), []
+        targets = PaddedTargets.of(targets)
         # MaxIoUAssigner(pos 0.7, neg 0.3, min_pos 0.3, match_low_quality) -- configs/_base_/models/mask_rcnn_swin_fpn.py:79-85; the anchors
         # are shared by the images
         inds_all = self.assign(flat_a, targets.boxes, targets.count, cfg["pos"], cfg["neg"], cfg["min_pos"], True)[0]
@@ -754,8 +782,8 @@ class MiniMaskRCNN(nn.Module):
         l_reg = ((reg_p - d_t).abs().sum(2) * pos_valid.float()).sum(1) / avg
         for b in range(B):                                                                        # per image, then over the batch in image order
             loss_cls, loss_reg = loss_cls + l_cls[b], loss_reg + l_reg[b]
-            with torch.no_grad():
-                proposals.append(self._proposals(cls_all[b], reg_all[b], anchors, cfg, img_hw)[0])
+        with torch.no_grad():                                                                     # once per batch; the RoI head takes a list
+            proposals = list(self.proposals(cls_all, reg_all, anchors, cfg, img_hw)[0].unbind(0))
         return loss_cls / B, loss_reg / B, proposals
 
     # -- RoI heads ------------------------------------------------------------------------------------------------------
@@ -844,9 +872,7 @@ class MiniMaskRCNN(nn.Module):
         anchors = make_anchors([f.shape[2:] for f in fpn], self.STRIDES, feats[0].device)
         cls_all, reg_all = self._rpn_flatten(rpn_outs)
         B, C, K = cls_all.shape[0], self.num_classes, cfg["max_per_img"]
-        props = [self._proposals(cls_all[b], reg_all[b], anchors, rpn_cfg, img_hw) for b in range(B)]
-        rois = torch.stack([p[0] for p in props])                                                 # [B, R, 4]
-        roi_count = (torch.stack([p[1] for p in props]) > -1e4).sum(1).to(torch.int32)            # the survivors of the RPN's NMS lead
+        rois, _, roi_count = self.proposals(cls_all, reg_all, anchors, rpn_cfg, img_hw)           # [B, R, 4]; the survivors of the RPN's NMS lead
         R = rois.shape[1]
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):
             x = self.roi_align(fpn[:4], self.STRIDES[:4], rois, 7)

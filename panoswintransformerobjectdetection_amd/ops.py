@@ -1680,6 +1680,78 @@ def mask_targets(masks, rois, gt_idx, pos_valid, size=28):
     return out
 
 
+def _level_sizes(level_sizes):
+    ns = (ctypes.c_int * len(level_sizes))(*[int(n) for n in level_sizes])
+    return ns, ctypes.cast(ns, ctypes.c_void_p)
+
+
+def rpn_proposals_supported(level_sizes, B, nms_pre, max_per_img):
+    """Whether pswin_rpn_proposals takes the shape: at most 8 levels, nms_pre <= 2048, P = min(max_per_img, sum of min(nms_pre, n_l))
+    <= 2048, B L <= 2048, B A < 2^31 and a workspace below 2^31 bytes (the entry point's own check, asked here without a launch)."""
+    if not 1 <= len(level_sizes) <= 8 or min(int(n) for n in level_sizes) < 1 or sum(int(n) for n in level_sizes) * int(B) >= 1 << 31:
+        return False
+    ns, nsp = _level_sizes(level_sizes)
+    return int(_lib.load().pswin_rpn_proposals_workspace(nsp, len(level_sizes), int(B), int(nms_pre), int(max_per_img))) > 0
+
+
+def rpn_proposals_rows_per_workgroup():
+    """The scores one workgroup of pswin_rpn_proposals sorts: the chunk of its reduction trees"""
+    return int(_lib.load().pswin_rpn_proposals_rows_per_workgroup())
+
+
+def rpn_proposals_launches(level_sizes, nms_pre, max_per_img):
+    """The kernel launches of one pswin_rpn_proposals call on these level sizes, whatever the batch"""
+    ns, nsp = _level_sizes(level_sizes)
+    n = int(_lib.load().pswin_rpn_proposals_launches(nsp, len(level_sizes), int(nms_pre), int(max_per_img)))
+    _lib.check(min(n, 0), "pswin_rpn_proposals_launches")
+    return n
+
+
+def rpn_proposals(scores, deltas, anchors, nms_pre, iou_thr, max_per_img, img_hw):
+    """detector.proposals_batch on the GPU (pswin_rpn_proposals): (rois f32 [B, P, 4], scores f32 [B, P], count int32 [B]) with
+    P = min(max_per_img, sum over the levels of min(nms_pre, n_l)) -- ALL P rows of every image as MiniMaskRCNN._proposals leaves them, the
+    suppressed tail (score -1e4) behind the count[b] survivors.  scores f32 [B, A] raw logits; deltas f32 [B, A, 4]; anchors: the list of
+    the levels' f32 [n_l, 4] tensors (make_anchors), A = their sum.  NaN scores and scores <= -1e4 are outside the contract.
+
+    LAUNCHES: rpn_proposals_launches(level sizes, nms_pre, max_per_img) kernels -- the selection passes (one per fourfold reduction of the
+    largest level's chunks of 8192 scores), the two launches of pswin_nms_groups, the passes of the final order -- plus the one
+    concatenation of the anchors: 7 for the five levels of a 512 x 1024 image with either cfg (3 + 2 + 1 + 1), for any batch size.  No
+    atomics, no host synchronisation, no host-to-device copy: the call can be captured, and a replay works on whatever the buffers hold
+    then.  The trees' partial lists, the decoded boxes and the NMS masks live in one workspace per (level sizes, B, nms_pre, max_per_img,
+    device), every part of it written by a call before the call reads it.  Limits: rpn_proposals_supported; beyond them PswinError.
+    CPU tensors: the definition."""
+    anchors = list(anchors)
+    if not scores.is_cuda:
+        from . import detector
+        return detector.proposals_batch(scores, deltas, anchors, dict(nms_pre=nms_pre, nms=iou_thr, max_per_img=max_per_img), img_hw)
+    if scores.dim() != 2 or deltas.dim() != 3 or tuple(deltas.shape) != tuple(scores.shape) + (4,) or not anchors or \
+            any(a.dim() != 2 or a.shape[1] != 4 or a.shape[0] < 1 for a in anchors) or sum(a.shape[0] for a in anchors) != scores.shape[1]:
+        raise PswinError(f"rpn_proposals: scores [B, A], deltas [B, A, 4] and per-level anchors [n_l, 4] that sum to A, got "
+                         f"{tuple(scores.shape)}, {tuple(deltas.shape)} and {[tuple(a.shape) for a in anchors]}")
+    dev = scores.device
+    if any(t.device != dev for t in [deltas] + anchors):
+        raise PswinError("rpn_proposals: scores, deltas and anchors must be on one device")
+    sizes = tuple(int(a.shape[0]) for a in anchors)
+    B, L = int(scores.shape[0]), len(sizes)
+    nms_pre, max_per_img, H, W = int(nms_pre), int(max_per_img), int(img_hw[0]), int(img_hw[1])
+    if not rpn_proposals_supported(sizes, B, nms_pre, max_per_img):
+        raise PswinError(f"rpn_proposals: outside the kernels' limits (levels <= 8, nms_pre <= 2048, P <= 2048, B L <= 2048, B A < 2^31): "
+                         f"level sizes {sizes}, B = {B}, nms_pre = {nms_pre}, max_per_img = {max_per_img}")
+    P = min(max_per_img, sum(min(nms_pre, n) for n in sizes))
+    scores, deltas = scores.detach().float().contiguous(), deltas.detach().float().contiguous()
+    flat = torch.cat([a.detach().float() for a in anchors], 0) if L > 1 else anchors[0].detach().float().contiguous()
+    ns, nsp = _level_sizes(sizes)
+    ws_key = ("proposals_ws", sizes, B, nms_pre, max_per_img, _dev_key(dev))
+    if ws_key not in _CACHE:
+        _CACHE[ws_key] = torch.empty(int(_lib.load().pswin_rpn_proposals_workspace(nsp, L, B, nms_pre, max_per_img)), dtype=torch.uint8, device=dev)
+    rois = torch.empty(B, P, 4, dtype=torch.float32, device=dev)
+    out_scores = torch.empty(B, P, dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    call("pswin_rpn_proposals", scores, ptr(scores), ptr(deltas), ptr(flat), nsp, L, B, nms_pre, ctypes.c_float(float(iou_thr)), max_per_img, H, W,
+         ptr(rois), ptr(out_scores), ptr(count), ptr(_CACHE[ws_key]))
+    return rois, out_scores, count
+
+
 def _lowp_or_f32(t):
     return t if t.dtype in (torch.float32, torch.bfloat16) else t.float()
 
