@@ -527,7 +527,13 @@ def test_fused_moves_of_the_layer_norm_kernels_equal_the_separate_row_movers(ops
     + shift + pad + partition (pswin_scatter_add_ln_fwd_map), and its backward kernel writes the bf16 branch gradient.  Both against
     the chain of separate kernels (window_scatter_add, layer_norm_gather, window_gather): every output and every gradient bit for bit,
     zero rows in the padding slots included (planar 14 x 21 has none)."""
-    B = 2
+    _fused_moves_case(ops, C, pano, H, W, shift, use_scale, 2)
+
+
+def _fused_moves_case(ops, C, pano, H, W, shift, use_scale, B):
+    """The body of the test above for a batch of B images (tests/test_kernel_trips_gpu.py runs it where the backward kernel's workgroups
+    walk the rows more than once).  The per-image scales: (0, 1.25) / (1.25, 0.5) for B = 2; for a larger batch every image gets a
+    scale of its own and a few get 0."""
     wmap, inv, nW = ops.window_maps(pano, H, W, shift, DEV)
     pads = ops.window_pads(pano, H, W, shift, DEV)
     assert pads.numel() == nW * 49 - H * W and bool((wmap[pads.long()] < 0).all())
@@ -535,8 +541,10 @@ def test_fused_moves_of_the_layer_norm_kernels_equal_the_separate_row_movers(ops
     ident = ops.identity_map(S, DEV)
     gamma, beta = det_uniform((C,), "fm:g", 0.5, 1.0), det_uniform((C,), "fm:b", 0.5)
     pbias, fbias = det_uniform((C,), "fm:pb", 0.5), det_uniform((C,), "fm:fb", 0.5)
-    s1 = torch.tensor([0.0, 1.25], device=DEV) if use_scale else None
-    s2 = torch.tensor([1.25, 0.5], device=DEV) if use_scale else None
+    v1 = [0.0, 1.25] if B == 2 else [0.0 if b % 5 == 1 else 0.75 + 0.125 * b for b in range(B)]
+    v2 = [1.25, 0.5] if B == 2 else [0.0 if b % 5 == 3 else 2.0 - 0.0625 * b for b in range(B)]
+    s1 = torch.tensor(v1, device=DEV) if use_scale else None
+    s2 = torch.tensor(v2, device=DEV) if use_scale else None
     x = det_uniform((B, S, C), "fm:x", 2.0)
     # (1) attention half: window-order input, token-order normalised output
     win = det_uniform((B, nW * 49, C), "fm:w", 2.0).to(torch.bfloat16)
@@ -692,7 +700,11 @@ def test_window_attention_module_against_the_reference_capture(ops, name, pano, 
 # ---- the per-window fused kernels: qkv -> attention -> proj (csrc/pswin_fused.hip, C = 96 / 3 heads) and qkv -> attention
 # (csrc/pswin_qkvattn.hip, C = 192 / 384), bf16 ------------------------------------------------------------------------------
 FUSED_CASES = [(2, 3, True, 0), (1, 5, False, 0), (3, 4, False, 3), (2, 3, False, 4), (2, 3, True, 3), (9, 2, True, 0),
-               (8, 15, True, 0), (1, 1, True, 0)]
+               (8, 15, True, 0), (1, 1, True, 0),
+               # more bias windows than the 256 persistent workgroups of win_fused_fwd_kernel (tests/test_kernel_trips_gpu.py checks that
+               # they stay so): one workgroup on a second trip -- three trips, the buffer parity back to 0, a per-window mask -- more
+               # images than waves on a second trip -- nb = B * nW through the per-image mask
+               (1, 257, True, 0), (2, 515, True, 3), (9, 300, False, 0), (2, 150, False, 4)]
 
 
 @pytest.mark.parametrize("B,nW,pano,mask_kind", FUSED_CASES)
