@@ -585,7 +585,9 @@ def batch_norm_relu(y, bn, training, pre_bias=None):
     use_batch = training or bn.running_mean is None
     if use_batch and bn.num_batches_tracked is not None and training:
         bn.num_batches_tracked.add_(1)
-    momentum = 0.1 if bn.momentum is None else bn.momentum
+    momentum = bn.momentum
+    if momentum is None:                                  # nn.BatchNorm2d's cumulative average: 1 / (batches seen, this one included)
+        momentum = 1.0 / float(bn.num_batches_tracked) if (training and bn.num_batches_tracked is not None) else 0.0
     return _BatchNormReLU.apply(y, bn.weight, bn.bias, bn.running_mean if (training or not use_batch) else None,
                                 bn.running_var if (training or not use_batch) else None, bn.eps, momentum, use_batch,
                                 pre_bias)

@@ -348,6 +348,33 @@ def test_batch_norm_relu(ops, C, dt, train):
     assert int(bn_dev.num_batches_tracked) == int(bn_ref.num_batches_tracked)
 
 
+def test_batch_norm_relu_cumulative_average(ops):
+    """momentum=None: nn.BatchNorm2d averages the batch statistics with weight 1 / num_batches_tracked.  Three training steps
+    against the module in float64; channel 3 has its mean at 30 standard deviations.  Tolerances of test_batch_norm_relu (fp32)."""
+    import copy
+    import torch.nn as nn
+    N, C, H, W = 2, 32, 37, 53
+    bn_ref = nn.BatchNorm2d(C, momentum=None)
+    with torch.no_grad():
+        bn_ref.weight.copy_(det_uniform((C,), "bnc:w", 0.5, 1.0)); bn_ref.bias.copy_(det_uniform((C,), "bnc:b", 0.5))
+        bn_ref.running_mean.copy_(det_uniform((C,), "bnc:rm", 0.3)); bn_ref.running_var.copy_(det_uniform((C,), "bnc:rv", 0.3, 1.0))
+    bn_dev = copy.deepcopy(bn_ref).to(DEV)
+    bn_ref = bn_ref.double()
+    bn_ref.train(); bn_dev.train()
+    pre = det_uniform((C,), "bnc:pre", 0.7)
+    for step in range(3):
+        off = det_uniform((1, C, 1, 1), f"bnc:off{step}", 1.5)
+        off[0, 3] = 30.0 * 2.0 / 3.0 ** 0.5                      # uniform in [-2, 2): a standard deviation of 2 / sqrt(3)
+        y = det_uniform((N, C, H, W), f"bnc:y{step}", 2.0) + off
+        ref = F.relu(bn_ref(y.double() + pre.double().view(1, C, 1, 1)))
+        yd = y.to(DEV).contiguous(memory_format=torch.channels_last)
+        out = ops.batch_norm_relu(yd, bn_dev, True, pre.to(DEV))
+        assert torch.allclose(out.double().cpu(), ref, rtol=1e-4, atol=1e-5)
+        assert torch.allclose(bn_dev.running_mean.double().cpu(), bn_ref.running_mean, rtol=1e-4, atol=1e-5), step
+        assert torch.allclose(bn_dev.running_var.double().cpu(), bn_ref.running_var, rtol=1e-4, atol=1e-5), step
+        assert int(bn_dev.num_batches_tracked) == int(bn_ref.num_batches_tracked) == step + 1
+
+
 @pytest.mark.parametrize("M,N,dt", [(275576 // 8, 288, torch.bfloat16), (1000, 96, torch.bfloat16), (98, 27648, torch.bfloat16),
                                     (5, 3072, torch.float32), (4097, 8, torch.float32)])
 def test_colsum(ops, M, N, dt):
