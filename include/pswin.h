@@ -208,6 +208,10 @@ int pswin_ln_workspace(long long rows, int C);
  * dres_sum is then only a flag and is not written) in `workspace`, and the caller sums them later, typically together
  * with every other parameter-gradient reduction of the backward pass through pswin_reduce_jobs. */
 int pswin_ln_partial_rows(long long rows, int C);
+/* Process-wide tuning hook of the LayerNorm family.  Rows of C == 96, 192, 384 or 768 elements whose operands lie within 32-bit byte
+ * offsets run on exact-row kernels (no chunk test, all loads of a row in flight together); the results are bitwise those of the generic
+ * kernels.  mode 0 = automatic (default), 1 = always the generic kernels (for tests and A/B measurements). */
+int pswin_ln_rows_tune(int mode);
 
 /* PatchMerging gather fused with its LayerNorm(4C) (HOT:563-574): y[b][i*W2+j] = LN(concat of the 4 tokens).
  * x: [B, H*W, C]; y: [B, H2*W2, 4C]; gamma, beta: f32 [4C]; mean, rstd: f32 [B, H2*W2]; C % 16 == 0, 4C <= 2048. */
