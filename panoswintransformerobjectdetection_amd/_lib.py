@@ -99,6 +99,10 @@ _PROTOTYPES = {
     "pswin_rpn_proposals_launches": [_vp, _i, _i, _i],
     "pswin_rpn_proposals_workspace": [_vp, _i, _i, _i, _i],
     "pswin_rpn_proposals": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "pswin_cascade_rows_per_workgroup": [],
+    "pswin_cascade_refine": [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp],
+    "pswin_giou_rows_fwd": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, ctypes.c_double, _vp, _vp],
+    "pswin_giou_rows_bwd": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, ctypes.c_double, _vp, _vp],
     "pswin_gemm_nt_supported": [ctypes.c_longlong, _i, _i],
     "pswin_gemm_nt": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],
     "pswin_gemm_nt_f32": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],

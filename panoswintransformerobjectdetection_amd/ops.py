@@ -1838,6 +1838,117 @@ def paste_masks(mask_logits, labels, boxes, count, thr, out_hw, out=None):
     return out
 
 
+def roi_targets_ranked(gt_inds, key, cand, gt, gt_labels, num_classes, n_pos_max, n_tot, stds):
+    """cascade.roi_targets_ranked on the GPU: roi_targets' five results and pos_rank int64 [B, n_pos_max], the ranks they were drawn by
+    (pswin_sample_ranks once, then one launch of pswin_roi_targets on those ranks).  Arguments and limits as roi_targets; capturable as
+    sample_ranks is.  CPU tensors: the definition."""
+    if not gt_inds.is_cuda:
+        from . import cascade
+        return cascade.roi_targets_ranked(gt_inds, key, cand, gt, gt_labels, num_classes, n_pos_max, n_tot, stds)
+    gt_inds, key = _sample_inputs("roi_targets_ranked", gt_inds, key)
+    B, N = (int(v) for v in gt_inds.shape)
+    dev = key.device
+    if tuple(cand.shape) != (B, N, 4) or gt.dim() != 3 or gt.shape[0] != B or gt.shape[2] != 4 or tuple(gt_labels.shape) != tuple(gt.shape[:2]) or \
+            gt_labels.dtype != torch.int64 or any(t.device != dev for t in (cand, gt, gt_labels)):
+        raise PswinError(f"roi_targets_ranked: cand [{B}, {N}, 4], gt [{B}, Gmax, 4] and int64 gt_labels [{B}, Gmax] on the device of gt_inds, got "
+                         f"{tuple(cand.shape)}, {tuple(gt.shape)} and {tuple(gt_labels.shape)} {gt_labels.dtype}")
+    n_pos_max, n_tot, Gmax = int(n_pos_max), int(n_tot), int(gt.shape[1])
+    cand, gt, gt_labels = cand.detach().float().contiguous(), gt.detach().float().contiguous(), gt_labels.contiguous()
+    pos_rank, neg_order = sample_ranks(gt_inds, key, n_pos_max, n_tot)
+    rois = torch.empty(B, n_tot, 4, dtype=torch.float32, device=dev)
+    labels = torch.empty(B, n_tot, dtype=torch.int64, device=dev)
+    reg_t = torch.empty(B, n_pos_max, 4, dtype=torch.float32, device=dev)
+    pos_valid = torch.empty(B, n_pos_max, dtype=torch.uint8, device=dev)
+    gt_idx = torch.empty(B, n_pos_max, dtype=torch.int64, device=dev)
+    std4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    call("pswin_roi_targets", key, ptr(gt_inds), ptr(pos_rank), ptr(neg_order), ptr(cand), ptr(gt), ptr(gt_labels), B, N, Gmax, n_pos_max, n_tot,
+         int(num_classes), ctypes.cast(std4, ctypes.c_void_p), ptr(rois), ptr(labels), ptr(reg_t), ptr(pos_valid), ptr(gt_idx))
+    return rois, labels, reg_t, pos_valid.view(torch.bool), gt_idx, pos_rank
+
+
+def cascade_rows_per_workgroup():
+    """The rows one workgroup of pswin_cascade_refine / pswin_giou_rows_fwd / _bwd takes"""
+    return int(_lib.load().pswin_cascade_rows_per_workgroup())
+
+
+def refine_rois(rois, cls, deltas, labels, stds, img_hw):
+    """cascade.refine_rois on the GPU in one launch (pswin_cascade_refine): (new_rois f32 [B, R, 4], used int64 [B, R]).  rois f32
+    [B, R, 4]; cls [B, R, C + 1] and deltas [B, R, 4 C], f32 or bf16, read in place (the box head's bf16 output under autocast is not
+    copied); labels int64 [B, R] or None.  C <= 128.  The argmax is torch.argmax's on the same values, ties included.  No gradient, no
+    host synchronisation: the call can be captured.  CPU tensors: the definition."""
+    if not cls.is_cuda:
+        from . import cascade
+        return cascade.refine_rois(rois, cls, deltas, labels, stds, img_hw)
+    if cls.dim() != 3 or tuple(rois.shape) != tuple(cls.shape[:2]) + (4,) or deltas.dim() != 3 or deltas.shape[:2] != cls.shape[:2] or \
+            deltas.shape[2] != 4 * (cls.shape[2] - 1) or cls.shape[2] < 2:
+        raise PswinError(f"refine_rois: rois [B, R, 4], cls [B, R, C + 1], deltas [B, R, 4 C], got {tuple(rois.shape)}, {tuple(cls.shape)}, "
+                         f"{tuple(deltas.shape)}")
+    B, R, C = int(cls.shape[0]), int(cls.shape[1]), int(cls.shape[2]) - 1
+    dev = cls.device
+    if labels is not None and (labels.dtype != torch.int64 or tuple(labels.shape) != (B, R) or labels.device != dev):
+        raise PswinError(f"refine_rois: labels must be an int64 [{B}, {R}] tensor on the device of the logits, or None")
+    if rois.device != dev or deltas.device != dev:
+        raise PswinError("refine_rois: rois, cls and deltas must be on one device")
+    rois = rois.detach().float().contiguous()
+    cls, deltas = _lowp_or_f32(cls.detach()).contiguous(), _lowp_or_f32(deltas.detach()).contiguous()
+    labels = None if labels is None else labels.contiguous()
+    new_rois = torch.empty(B, R, 4, dtype=torch.float32, device=dev)
+    used = torch.empty(B, R, dtype=torch.int64, device=dev)
+    std4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    call("pswin_cascade_refine", cls, ptr(rois), ptr(cls), dtype_code(cls), ptr(deltas), dtype_code(deltas), ptr(labels), B, R, C,
+         ctypes.cast(std4, ctypes.c_void_p), int(img_hw[0]), int(img_hw[1]), ptr(new_rois), ptr(used),
+         algo_bytes=B * R * (C * cls.element_size() + 4 * deltas.element_size() + 16 + 16 + 8))
+    return new_rois, used
+
+
+class _GIoURows(torch.autograd.Function):
+    """cascade.giou_rows as one node: the forward launch writes the [N] rows; the backward launch recomputes the forward from the saved
+    INPUTS (nothing else is kept) and writes every element of the [N, 4 C] gradient in the dtype of `deltas` -- no float copy of the
+    prediction, no zero fill, no scatter."""
+
+    @staticmethod
+    def forward(ctx, rois, deltas, labels, weight, target, stds, eps):
+        N, C = int(deltas.shape[0]), int(deltas.shape[1]) // 4
+        out = torch.empty(N, dtype=torch.float32, device=deltas.device)
+        std4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+        call("pswin_giou_rows_fwd", deltas, ptr(rois), ptr(deltas), dtype_code(deltas), ptr(labels), ptr(weight), ptr(target), N, C,
+             ctypes.cast(std4, ctypes.c_void_p), ctypes.c_double(float(eps)), ptr(out), algo_bytes=N * (4 * deltas.element_size() + 48))
+        ctx.save_for_backward(rois, deltas, labels, weight, target)
+        ctx.cfg = (tuple(float(v) for v in stds), float(eps))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        rois, deltas, labels, weight, target = ctx.saved_tensors
+        stds, eps = ctx.cfg
+        N, C = int(deltas.shape[0]), int(deltas.shape[1]) // 4
+        grad_rows = grad_rows.float().contiguous()
+        grad = torch.empty_like(deltas)
+        std4 = (ctypes.c_float * 4)(*stds)
+        call("pswin_giou_rows_bwd", deltas, ptr(rois), ptr(deltas), dtype_code(deltas), ptr(labels), ptr(weight), ptr(target), ptr(grad_rows), N, C,
+             ctypes.cast(std4, ctypes.c_void_p), ctypes.c_double(eps), ptr(grad), algo_bytes=N * (4 * C + 4) * deltas.element_size() + N * 52)
+        return None, grad, None, None, None, None, None
+
+
+def giou_rows(rois, deltas, labels, weight, target, stds, eps=1e-6):
+    """cascade.giou_rows on the GPU (pswin_giou_rows_fwd, and pswin_giou_rows_bwd for the gradient of `deltas`): f32 [N] = weight *
+    (1 - GIoU(decoded box, target)).  rois f32 [N, 4]; deltas [N, 4 C], f32 or bf16, read in place and the only input with a gradient;
+    labels int64 [N]; weight f32 [N]; target f32 [N, 4].  C <= 128.  One launch per direction, no atomics, no host synchronisation: the
+    call can be captured.  CPU tensors: the definition."""
+    if not deltas.is_cuda:
+        from . import cascade
+        return cascade.giou_rows(rois, deltas, labels, weight, target, stds, eps)
+    if deltas.dim() != 2 or deltas.shape[1] % 4 or deltas.shape[1] < 4 or tuple(rois.shape) != (deltas.shape[0], 4) or \
+            tuple(target.shape) != tuple(rois.shape) or tuple(labels.shape) != (deltas.shape[0],) or tuple(weight.shape) != tuple(labels.shape) or \
+            labels.dtype != torch.int64 or any(t.device != deltas.device for t in (rois, labels, weight, target)):
+        raise PswinError(f"giou_rows: rois [N, 4], deltas [N, 4 C], int64 labels [N], weight [N], target [N, 4] on one device, got "
+                         f"{tuple(rois.shape)}, {tuple(deltas.shape)}, {tuple(labels.shape)} {labels.dtype}, {tuple(weight.shape)}, {tuple(target.shape)}")
+    if deltas.dtype not in (torch.float32, torch.bfloat16):
+        raise PswinError(f"giou_rows: deltas must be float32 or bfloat16, got {deltas.dtype}")
+    return _GIoURows.apply(rois.detach().float().contiguous(), deltas.contiguous(), labels.contiguous(), weight.detach().float().contiguous(),
+                           target.detach().float().contiguous(), stds, eps)
+
+
 # ------------------------------------------------------------------------------------------------
 # qkv Linear + attention core in one kernel for C = 192 / 384 (pswin_qkv_attn_fused_fwd, round 3)
 # ------------------------------------------------------------------------------------------------
