@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PSWIN_LIB") or os.path.join(_PKG, "libpswin_hip.so") 
 F32, BF16 = 0, 1
 MODE_PLANAR, MODE_PANO = 0, 1
 WS, WTOK, WPAD, HEAD_DIM = 7, 49, 64, 32
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -103,6 +103,18 @@ _PROTOTYPES = {
     "pswin_cascade_refine": [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp],
     "pswin_giou_rows_fwd": [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, ctypes.c_double, _vp, _vp],
     "pswin_giou_rows_bwd": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, ctypes.c_double, _vp, _vp],
+    "pswin_losses_rows_per_workgroup": [],
+    "pswin_rpn_losses_chunk": [],
+    "pswin_ce_rows_fwd": [_vp, _i, _vp, _i, _i, _vp, _vp],
+    "pswin_ce_rows_bwd": [_vp, _i, _vp, _vp, _i, _i, _vp, _vp],
+    "pswin_l1_rows_fwd": [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "pswin_l1_rows_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "pswin_mask_bce_rows_fwd": [_vp, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i,
+                                _vp, _vp, _vp],
+    "pswin_mask_bce_rows_bwd": [_vp, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _vp, _i, _i,
+                                _i, _vp, _vp],
+    "pswin_rpn_losses_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "pswin_rpn_losses_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "pswin_gemm_nt_supported": [ctypes.c_longlong, _i, _i],
     "pswin_gemm_nt": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],
     "pswin_gemm_nt_f32": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],

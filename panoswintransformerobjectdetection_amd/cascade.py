@@ -277,7 +277,7 @@ class MiniCascadeRCNN(det.MiniMaskRCNN):
         labels_c = labels_b.reshape(-1)
         x = self.roi_align(feats[:4], self.STRIDES[:4], rois_b, 7)
         cls, reg = self.bbox_heads[i](x.to(feats[0].dtype))
-        loss_cls = F.cross_entropy(cls.float(), labels_c)
+        loss_cls = self.cls_loss(cls, labels_c)
         with torch.no_grad():
             bi = torch.arange(B, device=rois_b.device)[:, None]
             weight = torch.cat([pos_valid.float(), pos_valid.new_zeros(B, n_tot - n_pos_max, dtype=torch.float32)], 1).reshape(-1)
@@ -289,12 +289,10 @@ class MiniCascadeRCNN(det.MiniMaskRCNN):
         pv = pos_valid.reshape(-1).float()
         pl = labels_b[:, :n_pos_max].reshape(-1).clamp(max=self.num_classes - 1)
         xm = self.roi_align(feats[:4], self.STRIDES[:4], rois_b[:, :n_pos_max], 14)
-        logits = self.mask_heads[i](xm.to(feats[0].dtype)).float()
-        logit_c = logits[torch.arange(pl.numel(), device=pl.device), pl]
+        logits = self.mask_heads[i](xm.to(feats[0].dtype))
         with torch.no_grad():
             mt = self.mask_targets(targets.masks, rois_b[:, :n_pos_max], gt_idx, pos_valid, cfg["mask_size"])
-        lm = F.binary_cross_entropy_with_logits(logit_c, mt, reduction="none").mean((1, 2))
-        return loss_cls, loss_bbox, (lm * pv).sum() / pv.sum().clamp(min=1), cls, reg
+        return loss_cls, loss_bbox, self.mask_loss(logits, pl, mt, pv), cls, reg
 
     def _cascade_losses(self, feats, proposals, targets, img_hw):
         losses = {}

@@ -42,6 +42,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import losses
 from .backbone import SimplePanoSwinTransformer
 
 
@@ -698,6 +699,10 @@ class MiniMaskRCNN(nn.Module):
     proposals = staticmethod(proposals_batch_dispatch)    # the RPN's proposals (top nms_pre, decode, NMS, top max_per_img), once per batch
     multiclass_nms = staticmethod(multiclass_nms_batch)   # test time: softmax, decode, class-wise NMS, top K of a batch
     paste = staticmethod(paste_masks_dispatch)            # test time: the detections' masks pasted into the image
+    rpn_loss = staticmethod(losses.rpn_loss_dispatch)     # the RPN's two losses from the flattened outputs and rpn_targets' results
+    cls_loss = staticmethod(losses.cls_loss_dispatch)     # the box head's cross-entropy on its logits as they are
+    box_loss = staticmethod(losses.box_loss_dispatch)     # the box head's L1 on the deltas of every row's class
+    mask_loss = staticmethod(losses.mask_loss_dispatch)   # the mask head's BCE on the label's channel of its logits as they are
     BBOX_STDS = (0.1, 0.1, 0.2, 0.2)
 
     def __init__(self, backbone_cfg, num_classes=80):
@@ -764,7 +769,6 @@ class MiniMaskRCNN(nn.Module):
         B = rpn_outs[0][0].shape[0]
         flat_a = torch.cat(anchors, 0)
         cls_all, reg_all = self._rpn_flatten(rpn_outs)
-        loss_cls = loss_reg = cls_all.new_zeros(())
         n_pos_max, n_tot = int(cfg["num"] * cfg["pos_fraction"]), cfg["num"]
         targets = PaddedTargets.of(targets)
         # MaxIoUAssigner(pos 0.7, neg 0.3, min_pos 0.3, match_low_quality) -- configs/_base_/models/mask_rcnn_swin_fpn.py:79-85; the anchors
@@ -774,17 +778,10 @@ class MiniMaskRCNN(nn.Module):
         proto = cls_all.new_empty(flat_a.shape[0])
         key = torch.stack([self.rand_like(proto) for _ in range(B)])
         idx, valid, pos_valid, d_t = self.rpn_targets(inds_all, key, flat_a, targets.boxes, n_pos_max, n_tot)
-        tgt = torch.cat([torch.ones(n_pos_max, device=key.device), torch.zeros(n_tot, device=key.device)])
-        avg = valid.sum(1).clamp(min=1)                                                           # [B]
-        bce = F.binary_cross_entropy_with_logits(cls_all.gather(1, idx), tgt[None].expand(B, -1), reduction="none")
-        l_cls = (bce * valid).sum(1) / avg
-        reg_p = reg_all.gather(1, idx[:, :n_pos_max, None].expand(-1, -1, 4))
-        l_reg = ((reg_p - d_t).abs().sum(2) * pos_valid.float()).sum(1) / avg
-        for b in range(B):                                                                        # per image, then over the batch in image order
-            loss_cls, loss_reg = loss_cls + l_cls[b], loss_reg + l_reg[b]
+        loss_cls, loss_reg = self.rpn_loss(cls_all, reg_all, idx, valid, pos_valid, d_t)             # per image, then over the batch: already / B
         with torch.no_grad():                                                                     # once per batch; the RoI head takes a list
             proposals = list(self.proposals(cls_all, reg_all, anchors, cfg, img_hw)[0].unbind(0))
-        return loss_cls / B, loss_reg / B, proposals
+        return loss_cls, loss_reg, proposals
 
     # -- RoI heads ------------------------------------------------------------------------------------------------------
     def _roi_losses(self, feats, proposals, targets, img_hw):
@@ -806,25 +803,21 @@ class MiniMaskRCNN(nn.Module):
             key = torch.stack([keys(n) for n in targets.list_counts or [Gmax] * B])
             rois_b, labels_b, reg_t, pos_valid, gt_idx = self.roi_targets(inds_all, key, cand_all, targets.boxes, targets.labels,
                                                                           self.num_classes, n_pos_max, n_tot, (0.1, 0.1, 0.2, 0.2))
-            labels_c, reg_t, pv = labels_b.reshape(-1), reg_t.reshape(-1, 4), pos_valid.reshape(-1).float()
+            labels_c, pv = labels_b.reshape(-1), pos_valid.reshape(-1).float()
+            pl = labels_b[:, :n_pos_max].reshape(-1).clamp(max=self.num_classes - 1)
         x = self.roi_align(feats[:4], self.STRIDES[:4], rois_b, 7)
         cls, reg = self.bbox_head(x.to(feats[0].dtype))
-        loss_cls = F.cross_entropy(cls.float(), labels_c)
-        pos_sel = torch.cat([torch.arange(n_pos_max, device=rois_b.device) + b * n_tot for b in range(B)])
-        pl = labels_c[pos_sel].clamp(max=self.num_classes - 1)
-        ar = torch.arange(pos_sel.numel(), device=reg.device)
-        reg_p = reg.float()[pos_sel].view(-1, self.num_classes, 4)[ar, pl]
-        loss_bbox = ((reg_p - reg_t).abs().sum(1) * pv).sum() / (B * n_tot)
+        # the losses take the heads' outputs as they are (bf16 under autocast): no float copy, no indexing of a prediction (losses.py)
+        loss_cls = self.cls_loss(cls, labels_c)
+        loss_bbox = self.box_loss(reg, labels_b, reg_t, pos_valid)
         if targets.masks is None:                                                                 # Faster R-CNN: no mask branch
             return loss_cls, loss_bbox, None
         # masks on the positive RoIs (the first n_pos_max of every image)
         xm = self.roi_align(feats[:4], self.STRIDES[:4], rois_b[:, :n_pos_max], 14)
-        logits = self.mask_head(xm.to(feats[0].dtype)).float()                                    # [B * P, classes, 28, 28]
-        logit_c = logits[ar, pl]
+        logits = self.mask_head(xm.to(feats[0].dtype))                                            # [B * P, classes, 28, 28]
         with torch.no_grad():                                                                     # once per batch: the assigned bitmap only
             mt = self.mask_targets(targets.masks, rois_b[:, :n_pos_max], gt_idx, pos_valid, cfg["mask_size"])
-        lm = F.binary_cross_entropy_with_logits(logit_c, mt, reduction="none").mean((1, 2))
-        loss_mask = (lm * pv).sum() / pv.sum().clamp(min=1)
+        loss_mask = self.mask_loss(logits, pl, mt, pv)
         return loss_cls, loss_bbox, loss_mask
 
     def heads_loss(self, feats, targets, img_hw):

@@ -1950,6 +1950,204 @@ def giou_rows(rois, deltas, labels, weight, target, stds, eps=1e-6):
 
 
 # ------------------------------------------------------------------------------------------------
+# the detector's training losses, row by row (csrc/pswin_losses.hip; definitions: losses.py)
+# ------------------------------------------------------------------------------------------------
+# off: ce_rows / l1_rows / mask_bce_rows / rpn_losses evaluate the torch definitions of losses.py on the GPU
+LOSS_KERNELS = _on("loss_kernels")
+
+
+def losses_rows_per_workgroup():
+    """The rows one workgroup of the ce_rows / l1_rows kernels takes"""
+    return int(_lib.load().pswin_losses_rows_per_workgroup())
+
+
+def rpn_losses_chunk():
+    """The anchors one workgroup of pswin_rpn_losses_bwd owns"""
+    return int(_lib.load().pswin_rpn_losses_chunk())
+
+
+def _loss_input(name, what, t):
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise PswinError(f"{name}: {what} must be float32 or bfloat16, got {t.dtype}")
+
+
+class _CERows(torch.autograd.Function):
+    """losses.ce_rows as one node: only the inputs are saved, the backward launch recomputes the row statistics and writes every element of
+    the [N, C + 1] gradient in the dtype of `cls`."""
+
+    @staticmethod
+    def forward(ctx, cls, labels):
+        N, C = int(cls.shape[0]), int(cls.shape[1]) - 1
+        out = torch.empty(N, dtype=torch.float32, device=cls.device)
+        call("pswin_ce_rows_fwd", cls, ptr(cls), dtype_code(cls), ptr(labels), N, C, ptr(out), algo_bytes=N * ((C + 1) * cls.element_size() + 12))
+        ctx.save_for_backward(cls, labels)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        cls, labels = ctx.saved_tensors
+        N, C = int(cls.shape[0]), int(cls.shape[1]) - 1
+        grad_rows = grad_rows.float().contiguous()
+        grad = torch.empty_like(cls)
+        call("pswin_ce_rows_bwd", cls, ptr(cls), dtype_code(cls), ptr(labels), ptr(grad_rows), N, C, ptr(grad),
+             algo_bytes=N * (2 * (C + 1) * cls.element_size() + 12))
+        return grad, None
+
+
+def ce_rows(cls, labels):
+    """losses.ce_rows on the GPU (pswin_ce_rows_fwd, and pswin_ce_rows_bwd for the gradient of `cls`): f32 [N] = logsumexp(row) -
+    row[label].  cls [N, C + 1], f32 or bf16, read in place; labels int64 [N], a label outside [0, C] gives a zero row.  C <= 128.  One
+    launch per direction, no atomics, no host synchronisation: the call can be captured.  CPU tensors: the definition."""
+    if not cls.is_cuda or not LOSS_KERNELS:
+        from . import losses
+        return losses.ce_rows(cls, labels)
+    if cls.dim() != 2 or cls.shape[1] < 2 or tuple(labels.shape) != (cls.shape[0],) or labels.dtype != torch.int64 or labels.device != cls.device:
+        raise PswinError(f"ce_rows: cls [N, C + 1] and int64 labels [N] on one device, got {tuple(cls.shape)}, {tuple(labels.shape)} {labels.dtype}")
+    _loss_input("ce_rows", "cls", cls)
+    return _CERows.apply(cls.contiguous(), labels.contiguous())
+
+
+class _L1Rows(torch.autograd.Function):
+    """losses.l1_rows as one node, as _GIoURows: inputs saved, every element of the [N, 4 C] gradient written in the dtype of `reg`."""
+
+    @staticmethod
+    def forward(ctx, reg, labels, weight, target):
+        N, C = int(reg.shape[0]), int(reg.shape[1]) // 4
+        out = torch.empty(N, dtype=torch.float32, device=reg.device)
+        call("pswin_l1_rows_fwd", reg, ptr(reg), dtype_code(reg), ptr(labels), ptr(weight), ptr(target), N, C, ptr(out),
+             algo_bytes=N * (4 * reg.element_size() + 32))
+        ctx.save_for_backward(reg, labels, weight, target)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        reg, labels, weight, target = ctx.saved_tensors
+        N, C = int(reg.shape[0]), int(reg.shape[1]) // 4
+        grad_rows = grad_rows.float().contiguous()
+        grad = torch.empty_like(reg)
+        call("pswin_l1_rows_bwd", reg, ptr(reg), dtype_code(reg), ptr(labels), ptr(weight), ptr(target), ptr(grad_rows), N, C, ptr(grad),
+             algo_bytes=N * (4 * C + 4) * reg.element_size() + N * 36)
+        return grad, None, None, None
+
+
+def l1_rows(reg, labels, weight, target):
+    """losses.l1_rows on the GPU (pswin_l1_rows_fwd / _bwd): f32 [N] = weight * sum_4 |reg[n, 4 lab : 4 lab + 4] - target[n]|.  reg
+    [N, 4 C], f32 or bf16, read in place and the only input with a gradient; labels int64 [N] (clamped to [0, C)); weight f32 [N]; target
+    f32 [N, 4].  C <= 128.  Capturable as giou_rows is.  CPU tensors: the definition."""
+    if not reg.is_cuda or not LOSS_KERNELS:
+        from . import losses
+        return losses.l1_rows(reg, labels, weight, target)
+    if reg.dim() != 2 or reg.shape[1] % 4 or reg.shape[1] < 4 or tuple(target.shape) != (reg.shape[0], 4) or tuple(labels.shape) != (reg.shape[0],) or \
+            tuple(weight.shape) != tuple(labels.shape) or labels.dtype != torch.int64 or any(t.device != reg.device for t in (labels, weight, target)):
+        raise PswinError(f"l1_rows: reg [N, 4 C], int64 labels [N], weight [N], target [N, 4] on one device, got {tuple(reg.shape)}, "
+                         f"{tuple(labels.shape)} {labels.dtype}, {tuple(weight.shape)}, {tuple(target.shape)}")
+    _loss_input("l1_rows", "reg", reg)
+    return _L1Rows.apply(reg.contiguous(), labels.contiguous(), weight.detach().float().contiguous(), target.detach().float().contiguous())
+
+
+def _mask_strides(logits):
+    """the element strides of dense [M, C, S, S] logits as pswin_mask_bce_rows_* takes them (a channel dimension of size 1 may carry any
+    stride: the NCHW ones are passed), or None if the memory is neither NCHW nor channels-last"""
+    M, C, S, _ = (int(v) for v in logits.shape)
+    if logits.is_contiguous():
+        return C * S * S, S * S, S, 1
+    if logits.is_contiguous(memory_format=torch.channels_last):
+        return C * S * S, 1, S * C, C
+    return None
+
+
+class _MaskBCERows(torch.autograd.Function):
+    """losses.mask_bce_rows as one node: the forward reads the label's channel through the logits' strides and leaves it as f32 [M, S, S];
+    that copy (1 / C of the logits) is what is saved -- the C-channel logits are NOT kept alive until the backward -- and the backward
+    writes every element of a gradient with the logits' shape, dtype and strides in memory order."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, target, weight):
+        M, C, S, _ = (int(v) for v in logits.shape)
+        out = torch.empty(M, dtype=torch.float32, device=logits.device)
+        picked = torch.empty(M, S, S, dtype=torch.float32, device=logits.device) if ctx.needs_input_grad[0] else None
+        call("pswin_mask_bce_rows_fwd", logits, ptr(logits), dtype_code(logits), *_mask_strides(logits), ptr(labels), ptr(target), ptr(weight), M, C, S,
+             ptr(out), ptr(picked), algo_bytes=M * (S * S * (logits.element_size() + 8) + 16))
+        ctx.save_for_backward(picked, labels, target, weight)
+        ctx.like = (logits.shape, logits.stride(), logits.dtype, _mask_strides(logits))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        picked, labels, target, weight = ctx.saved_tensors
+        shape, stride, dtype, strides = ctx.like
+        M, C, S, _ = (int(v) for v in shape)
+        grad_rows = grad_rows.float().contiguous()
+        grad = torch.empty_strided(shape, stride, dtype=dtype, device=picked.device)
+        call("pswin_mask_bce_rows_bwd", grad, ptr(picked), dtype_code(grad), *strides, ptr(labels), ptr(target), ptr(weight), ptr(grad_rows), M, C, S,
+             ptr(grad), algo_bytes=M * (S * S * (C * grad.element_size() + 8) + 20))
+        return grad, None, None, None
+
+
+def mask_bce_rows(logits, labels, target, weight):
+    """losses.mask_bce_rows on the GPU (pswin_mask_bce_rows_fwd / _bwd): f32 [M] = weight * mean over the map of BCE-with-logits of
+    logits[m, lab_m] against target[m].  logits [M, C, S, S], f32 or bf16, NCHW or channels-last memory, read in place (any other memory is
+    copied to NCHW first) and the only input with a gradient, which has the logits' strides; labels int64 [M] (clamped to [0, C)); target
+    f32 [M, S, S]; weight f32 [M].  C <= 128, S <= 56.  Capturable.  CPU tensors: the definition."""
+    if not logits.is_cuda or not LOSS_KERNELS:
+        from . import losses
+        return losses.mask_bce_rows(logits, labels, target, weight)
+    if logits.dim() != 4 or logits.shape[2] != logits.shape[3] or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]) or \
+            tuple(labels.shape) != (logits.shape[0],) or tuple(weight.shape) != tuple(labels.shape) or labels.dtype != torch.int64 or \
+            any(t.device != logits.device for t in (labels, target, weight)):
+        raise PswinError(f"mask_bce_rows: logits [M, C, S, S], int64 labels [M], target [M, S, S], weight [M] on one device, got "
+                         f"{tuple(logits.shape)}, {tuple(labels.shape)} {labels.dtype}, {tuple(target.shape)}, {tuple(weight.shape)}")
+    _loss_input("mask_bce_rows", "logits", logits)
+    if _mask_strides(logits) is None:
+        logits = logits.contiguous()
+    return _MaskBCERows.apply(logits, labels.contiguous(), target.detach().float().contiguous(), weight.detach().float().contiguous())
+
+
+class _RpnLosses(torch.autograd.Function):
+    """losses.rpn_losses as one node: the backward launch writes every element of both [B, A] and [B, A, 4] gradients -- the sampled values
+    at the valid slots' anchors, zeros everywhere else -- without a zero fill or a scatter."""
+
+    @staticmethod
+    def forward(ctx, cls_all, reg_all, idx, valid, pos_valid, reg_t):
+        (B, A), S, P = (int(v) for v in cls_all.shape), int(idx.shape[1]), int(pos_valid.shape[1])
+        out = torch.empty(B, 2, dtype=torch.float32, device=cls_all.device)
+        call("pswin_rpn_losses_fwd", cls_all, ptr(cls_all), ptr(reg_all), ptr(idx), ptr(valid), ptr(pos_valid), ptr(reg_t), B, A, S, P, ptr(out),
+             algo_bytes=B * (S * 16 + P * 33))
+        ctx.save_for_backward(cls_all, reg_all, idx, valid, pos_valid, reg_t)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        cls_all, reg_all, idx, valid, pos_valid, reg_t = ctx.saved_tensors
+        (B, A), S, P = (int(v) for v in cls_all.shape), int(idx.shape[1]), int(pos_valid.shape[1])
+        grad_out = grad_out.float().contiguous()
+        grad_cls, grad_reg = torch.empty_like(cls_all), torch.empty_like(reg_all)
+        call("pswin_rpn_losses_bwd", cls_all, ptr(cls_all), ptr(reg_all), ptr(idx), ptr(valid), ptr(pos_valid), ptr(reg_t), ptr(grad_out), B, A, S, P,
+             ptr(grad_cls), ptr(grad_reg), algo_bytes=B * A * 20)
+        return grad_cls, grad_reg, None, None, None, None
+
+
+def rpn_losses(cls_all, reg_all, idx, valid, pos_valid, reg_t):
+    """losses.rpn_losses on the GPU (pswin_rpn_losses_fwd / _bwd): f32 [B, 2], the class BCE and the box L1 of every image's sampled
+    anchors, each divided by max(the image's valid slots, 1).  cls_all f32 [B, A] and reg_all f32 [B, A, 4] (the inputs with a gradient);
+    idx int64 [B, S], valid f32 [B, S], pos_valid bool [B, P], reg_t f32 [B, P, 4]: what rpn_targets returns, P <= S.  Capturable.
+    CPU tensors: the definition."""
+    if not cls_all.is_cuda or not LOSS_KERNELS:
+        from . import losses
+        return losses.rpn_losses(cls_all, reg_all, idx, valid, pos_valid, reg_t)
+    ok = cls_all.dim() == 2 and tuple(reg_all.shape) == tuple(cls_all.shape) + (4,) and idx.dim() == 2 and idx.shape[0] == cls_all.shape[0] and \
+        tuple(valid.shape) == tuple(idx.shape) and pos_valid.dim() == 2 and pos_valid.shape[0] == idx.shape[0] and \
+        1 <= pos_valid.shape[1] <= idx.shape[1] and tuple(reg_t.shape) == tuple(pos_valid.shape) + (4,)
+    if not ok or idx.dtype != torch.int64 or pos_valid.dtype not in (torch.bool, torch.uint8) or cls_all.dtype != torch.float32 or \
+            reg_all.dtype != torch.float32 or any(t.device != cls_all.device for t in (reg_all, idx, valid, pos_valid, reg_t)):
+        raise PswinError(f"rpn_losses: float32 cls_all [B, A] and reg_all [B, A, 4], int64 idx [B, S], valid [B, S], bool pos_valid [B, P], reg_t "
+                         f"[B, P, 4], P <= S, on one device, got {tuple(cls_all.shape)} {cls_all.dtype}, {tuple(reg_all.shape)} {reg_all.dtype}, "
+                         f"{tuple(idx.shape)} {idx.dtype}, {tuple(valid.shape)}, {tuple(pos_valid.shape)} {pos_valid.dtype}, {tuple(reg_t.shape)}")
+    return _RpnLosses.apply(cls_all.contiguous(), reg_all.contiguous(), idx.contiguous(), valid.detach().float().contiguous(),
+                            pos_valid.contiguous().view(torch.uint8), reg_t.detach().float().contiguous())
+
+
+# ------------------------------------------------------------------------------------------------
 # qkv Linear + attention core in one kernel for C = 192 / 384 (pswin_qkv_attn_fused_fwd, round 3)
 # ------------------------------------------------------------------------------------------------
 # off: the unfused chain qkv GEMM -> pswin_attn_fwd
