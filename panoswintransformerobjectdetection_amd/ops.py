@@ -583,14 +583,16 @@ def batch_norm_relu(y, bn, training, pre_bias=None):
     """ReLU(BatchNorm2d(y + pre_bias)) for a channels-last y with the parameters / buffers of the nn.BatchNorm2d
     module `bn`; pre_bias (the convolution bias) is never materialised on the activation."""
     use_batch = training or bn.running_mean is None
-    if use_batch and bn.num_batches_tracked is not None and training:
-        bn.num_batches_tracked.add_(1)
+    counted = training and bn.num_batches_tracked is not None
     momentum = bn.momentum
     if momentum is None:                                  # nn.BatchNorm2d's cumulative average: 1 / (batches seen, this one included)
-        momentum = 1.0 / float(bn.num_batches_tracked) if (training and bn.num_batches_tracked is not None) else 0.0
-    return _BatchNormReLU.apply(y, bn.weight, bn.bias, bn.running_mean if (training or not use_batch) else None,
-                                bn.running_var if (training or not use_batch) else None, bn.eps, momentum, use_batch,
-                                pre_bias)
+        momentum = 1.0 / (float(bn.num_batches_tracked) + 1.0) if counted else 0.0
+    z = _BatchNormReLU.apply(y, bn.weight, bn.bias, bn.running_mean if (training or not use_batch) else None,
+                             bn.running_var if (training or not use_batch) else None, bn.eps, momentum, use_batch,
+                             pre_bias)
+    if counted:                                           # only a batch the kernel accepted is counted
+        bn.num_batches_tracked.add_(1)
+    return z
 
 
 def colsum(x2d, zero_cols=None, owners=()):
