@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSWIN_ABI_VERSION 6
+#define PSWIN_ABI_VERSION 7
 
 #define PSWIN_F32 0
 #define PSWIN_BF16 1
@@ -987,6 +987,56 @@ int pswin_rpn_losses_fwd(const float* cls_all, const float* reg_all, const long 
                          const float* reg_t, int B, int A, int S, int P, float* out, void* stream);
 int pswin_rpn_losses_bwd(const float* cls_all, const float* reg_all, const long long* idx, const float* valid, const unsigned char* pos_valid,
                          const float* reg_t, const float* grad_out, int B, int A, int S, int P, float* grad_cls, float* grad_reg, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mean average precision of a padded batch's detections (csrc/pswin_eval.hip; panoswintransformerobjectdetection_amd/evaluation.py:
+ * box_iou_pairs, mask_iou_pairs, match_pairs, average_precision_sorted, MapAccumulator)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Common to the entry points below: a batch is a Detections (boxes f32 [B][K][4], scores f32 [B][K], labels int64 [B][K], count int32 [B])
+ * and a PaddedTargets (boxes f32 [B][G][4], labels int64 [B][G], count int32 [B]), read in place with both counts from the device; no host
+ * synchronisation, no data-dependent shape, every output element written by plain stores (the ground-truth histogram: integer atomic
+ * adds, whose result has no order).  1 <= B <= 65535, 1 <= K <= 1024, G >= 1, B K G < 2^31; anything else is PSWIN_ERR_ARG, checked
+ * before the device is touched. */
+int pswin_ap_segments_chunk(void);                               /* records one workgroup of pswin_ap_segments takes per trip */
+
+/* iou f32 [B][K][G]: bbox_overlaps' float32 expression, overlap / max(area_d + area_g - overlap, 1e-6) in that order of operations, for
+ * the pairs with k < det_count[b], g < gt_count[b] and equal labels; -1 for every other pair.  det_area f32 [B][K] and gt_area f32 [B][G]
+ * (either may be NULL): (x2 - x1) (y2 - y1) in float32 of EVERY row.  16-byte aligned boxes. */
+int pswin_box_iou_pairs(const float* det_boxes, const long long* det_labels, const int* det_count, const float* gt_boxes,
+                        const long long* gt_labels, const int* gt_count, int B, int K, int G, float* iou, float* det_area, float* gt_area,
+                        void* stream);
+
+/* The same for bitmaps: det_masks uint8 [B][K][H][W], gt_masks uint8 [B][G][H][W], a pixel counts where its byte is not zero.
+ * iou = float(double(inter) / double(area_d + area_g - inter)), 0 when the union is 0, for the pairs as above, -1 elsewhere; det_area /
+ * gt_area (required): the pixel counts as f32, 0 for a row past its count.  Areas are counted once per counted mask and intersections only
+ * for the pairs as above: H W bytes per counted mask plus 2 H W per pair are read, nothing else of the masks.  workspace:
+ * pswin_mask_iou_workspace(B, K, G) bytes.  H W must be a multiple of 16 (16-byte loads) and the masks 16-byte aligned. */
+int pswin_mask_iou_workspace(int B, int K, int G);
+int pswin_mask_iou_pairs(const unsigned char* det_masks, const long long* det_labels, const int* det_count, const unsigned char* gt_masks,
+                         const long long* gt_labels, const int* gt_count, int B, int K, int G, int H, int W, float* iou, float* det_area,
+                         float* gt_area, void* workspace, void* stream);
+
+/* tpfp_default for a batch (evaluation.match_pairs).  iou as above (a negative entry is no candidate); ignore uint8 [B][G] or NULL;
+ * iou_thrs: T floats in (0, 1] and area_ranges: S pairs (min_area, max_area) or NULL with S = 1, both HOST arrays read during the call;
+ * T <= 16, S <= 8.  marks uint8 [T][S][B][K]: 0 ignored or past the count, 1 true positive, 2 false positive.  A detection can only
+ * match the box of its best IoU (ties: regular before ignored, then the lower index); below the threshold it is a false positive if its
+ * own area is in the range; on an ignored box or one outside the range it is ignored; else it is a true positive exactly when no
+ * detection in front of it in (descending score, ascending row) chose the same box with an IoU at or above the threshold.
+ * The accumulator: image b goes to slot cursor[0] + b (cursor: device int32, read only).  rec_score f32 / rec_label int32 [capacity][K]
+ * (label C for a row past the count or outside [0, C)) and rec_marks uint8 [T][S][capacity][K] get the slot's rows; num_gts int32 [S][C]
+ * gains the image's regular boxes per (range, class).  A slot outside [0, capacity) writes nothing but overflow[0] = 1. */
+int pswin_eval_match(const float* iou, const float* det_scores, const long long* det_labels, const int* det_count, const long long* gt_labels,
+                     const int* gt_count, const unsigned char* ignore, const float* det_area, const float* gt_area, const float* iou_thrs, int T,
+                     const float* area_ranges, int S, int B, int K, int G, int C, int capacity, const int* cursor, unsigned char* marks,
+                     float* rec_score, int* rec_label, unsigned char* rec_marks, int* num_gts, int* overflow, void* stream);
+
+/* average_precision(mode='area') per (threshold, range, class): marks_sorted uint8 [T S][N], the records' marks in the order (class,
+ * descending score); bounds int32 [C + 1], class c owning records bounds[c] .. bounds[c + 1] - 1; num_gts int32 [S][C] -> ap f32 [T][S][C].
+ * Integer counts, precision float32(tp / max(tp + fp, eps)), recall and the sum in double in a fixed order; 0 where num_gts is 0.
+ * N <= 2^24 (the counts stay exact in float32). */
+int pswin_ap_segments(const unsigned char* marks_sorted, const int* bounds, const int* num_gts, int T, int S, int C, long long N, float* ap,
+                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PSWIN_LIB") or os.path.join(_PKG, "libpswin_hip.so") 
 F32, BF16 = 0, 1
 MODE_PLANAR, MODE_PANO = 0, 1
 WS, WTOK, WPAD, HEAD_DIM = 7, 49, 64, 32
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -115,6 +115,13 @@ _PROTOTYPES = {
                                 _i, _vp, _vp],
     "pswin_rpn_losses_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "pswin_rpn_losses_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "pswin_ap_segments_chunk": [],
+    "pswin_box_iou_pairs": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "pswin_mask_iou_workspace": [_i, _i, _i],
+    "pswin_mask_iou_pairs": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "pswin_eval_match": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                         _vp],
+    "pswin_ap_segments": [_vp, _vp, _vp, _i, _i, _i, ctypes.c_longlong, _vp, _vp],
     "pswin_gemm_nt_supported": [ctypes.c_longlong, _i, _i],
     "pswin_gemm_nt": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],
     "pswin_gemm_nt_f32": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],

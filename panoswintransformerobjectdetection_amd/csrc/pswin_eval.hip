@@ -1,0 +1,435 @@
+// Mean average precision of a padded batch's detections on the device (panoswintransformerobjectdetection_amd/evaluation.py:
+// box_iou_pairs, mask_iou_pairs, match_pairs, average_precision_sorted) -- gfx950 only.
+//
+// Everything is read from device memory in place: a Detections' and a PaddedTargets' buffers with both counts, the accumulator's cursor.
+// Nothing is read back, no shape depends on the data, every store is a plain vector store.  The only atomics are INTEGER adds (the
+// ground-truth histogram), whose result does not depend on their order.
+//
+// PAIR IOU (box_iou_pairs_kernel): one lane per (image, detection, box).  The float32 expression of the reference's bbox_overlaps in its
+// order of operations (the library is built with -ffp-contract=off, the division is correctly rounded): bit-identical IoUs, so the
+// comparisons with a threshold that the marks hang on are the reference's.  A pair outside the counts or of two classes is -1.
+//
+// MASK IOU: mask_area_kernel counts the non-zero bytes of every counted mask once (one workgroup per mask, 16-byte loads);
+// mask_pair_kernel takes one workgroup per (image, detection, box), leaves at once unless the pair is inside both counts and of one class,
+// and counts the bytes that are non-zero in both.  Integer counts: no order of summation to fix.  IoU = float(double(inter) / double(union)).
+//
+// MATCH (eval_match_kernel): one workgroup per image.  A wavefront takes a detection and its 64 lanes stride over the Gmax columns, each
+// keeping its best (IoU, then regular before ignored, then lower index); a butterfly over the lanes merges them by the same total order,
+// so the answer does not depend on how the columns fell on the lanes.  Then one lane per detection finds the largest best-IoU among the
+// detections that precede it in (descending score, ascending row) and chose the same box: the detection is a true positive at a
+// threshold exactly when that maximum is below the threshold, which is tpfp_default's gt_covered flag without its sequential loop.
+//
+// AP (ap_segments_kernel): one workgroup per (threshold, range, class) over that class's records in sorted order.  A forward pass in
+// chunks of AP_CHUNK records gives the totals of true and false positives; a backward pass, chunk by chunk from the segment's end, carries
+// the counts behind the chunk and the running maximum of precision, and adds (recall step) x (precision made monotone from the right) at
+// every true positive in double.  The order of every addition is fixed by the thread and chunk indices.
+#include "pswin_common.hpp"
+
+namespace {
+using namespace pswin;
+
+constexpr int EVAL_THREADS = 256;
+constexpr int EVAL_MAX_K = 1024;      // detections per image the match kernel keeps in LDS
+constexpr int EVAL_MAX_T = 16;
+constexpr int EVAL_MAX_S = 8;
+constexpr int AP_PER_THREAD = 4;
+constexpr int AP_CHUNK = EVAL_THREADS * AP_PER_THREAD;
+constexpr float F32_EPS = 1.1920928955078125e-07f;       // np.finfo(np.float32).eps
+
+struct MatchCfg {
+    float thr[EVAL_MAX_T];
+    float lo[EVAL_MAX_S], hi[EVAL_MAX_S];
+    int T, S, ranged;
+};
+
+__device__ inline bool in_range(const MatchCfg& cfg, int s, float area) { return !cfg.ranged || (area >= cfg.lo[s] && area < cfg.hi[s]); }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// pair IoU of boxes
+// ---------------------------------------------------------------------------------------------------------------------------------
+__device__ inline float box_area(f32x4 b) { return (b[2] - b[0]) * (b[3] - b[1]); }
+
+__global__ __launch_bounds__(EVAL_THREADS) void box_iou_pairs_kernel(const float* __restrict__ db, const long long* __restrict__ dl,
+                                                                    const int* __restrict__ dc, const float* __restrict__ gb,
+                                                                    const long long* __restrict__ gl, const int* __restrict__ gc, int K, int G,
+                                                                    int total, float* __restrict__ iou, float* __restrict__ det_area,
+                                                                    float* __restrict__ gt_area) {
+    const int i = blockIdx.x * EVAL_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int g = i % G, k = (i / G) % K, b = i / (G * K);
+    const f32x4 d = *reinterpret_cast<const f32x4*>(db + ((size_t)b * K + k) * 4);
+    const f32x4 q = *reinterpret_cast<const f32x4*>(gb + ((size_t)b * G + g) * 4);
+    const float a1 = box_area(d), a2 = box_area(q);
+    float v = -1.f;
+    if (k < dc[b] && g < gc[b] && dl[(size_t)b * K + k] == gl[(size_t)b * G + g]) {
+        const float xs = fmaxf(d[0], q[0]), ys = fmaxf(d[1], q[1]), xe = fminf(d[2], q[2]), ye = fminf(d[3], q[3]);
+        const float overlap = fmaxf(xe - xs, 0.f) * fmaxf(ye - ys, 0.f);
+        const float uni = fmaxf(a1 + a2 - overlap, 1e-6f);
+        v = overlap / uni;
+    }
+    iou[i] = v;
+    if (g == 0 && det_area) det_area[(size_t)b * K + k] = a1;
+    if (k == 0 && gt_area) gt_area[(size_t)b * G + g] = a2;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// pair IoU of bitmaps
+// ---------------------------------------------------------------------------------------------------------------------------------
+// bit 7 of every byte of w that is not zero
+__device__ inline unsigned nz_bytes(unsigned w) { return (((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u; }
+
+// the sum of v over the workgroup's 256 threads, in every thread (integers: the order does not matter)
+__device__ inline int block_sum_int(int v, int* lds4) {
+    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return lds4[0] + lds4[1] + lds4[2] + lds4[3];
+}
+
+// grid B (K + G): row r < K of an image is detection r, the others box r - K.  areas: int [B][K + G]
+__global__ __launch_bounds__(EVAL_THREADS) void mask_area_kernel(const unsigned char* __restrict__ dm, const int* __restrict__ dc,
+                                                                const unsigned char* __restrict__ gm, const int* __restrict__ gc, int K, int G,
+                                                                int vecs, int* __restrict__ areas, float* __restrict__ det_area,
+                                                                float* __restrict__ gt_area) {
+    __shared__ int lds4[4];
+    const int r = blockIdx.x % (K + G), b = blockIdx.x / (K + G);
+    const bool is_det = r < K;
+    const int row = is_det ? r : r - K;
+    const bool counted = row < (is_det ? dc[b] : gc[b]);
+    int n = 0;
+    if (counted) {         // uniform over the workgroup
+        const size_t m = is_det ? (size_t)b * K + row : (size_t)b * G + row;
+        const u32x4* p = reinterpret_cast<const u32x4*>((is_det ? dm : gm) + m * (size_t)vecs * 16);
+        for (int v = threadIdx.x; v < vecs; v += EVAL_THREADS) {
+            const u32x4 w = p[v];
+            n += __popc(nz_bytes(w[0])) + __popc(nz_bytes(w[1])) + __popc(nz_bytes(w[2])) + __popc(nz_bytes(w[3]));
+        }
+        n = block_sum_int(n, lds4);
+    }
+    if (threadIdx.x == 0) {
+        areas[blockIdx.x] = n;
+        if (is_det) det_area[(size_t)b * K + row] = (float)n;
+        else gt_area[(size_t)b * G + row] = (float)n;
+    }
+}
+
+// grid B K G
+__global__ __launch_bounds__(EVAL_THREADS) void mask_pair_kernel(const unsigned char* __restrict__ dm, const long long* __restrict__ dl,
+                                                                const int* __restrict__ dc, const unsigned char* __restrict__ gm,
+                                                                const long long* __restrict__ gl, const int* __restrict__ gc, int K, int G,
+                                                                int vecs, const int* __restrict__ areas, float* __restrict__ iou) {
+    __shared__ int lds4[4];
+    const int g = blockIdx.x % G, k = (blockIdx.x / G) % K, b = blockIdx.x / (G * K);
+    if (!(k < dc[b] && g < gc[b] && dl[(size_t)b * K + k] == gl[(size_t)b * G + g])) {      // uniform: nothing of either mask is read
+        if (threadIdx.x == 0) iou[blockIdx.x] = -1.f;
+        return;
+    }
+    const u32x4* pd = reinterpret_cast<const u32x4*>(dm + ((size_t)b * K + k) * (size_t)vecs * 16);
+    const u32x4* pg = reinterpret_cast<const u32x4*>(gm + ((size_t)b * G + g) * (size_t)vecs * 16);
+    int n = 0;
+    for (int v = threadIdx.x; v < vecs; v += EVAL_THREADS) {
+        const u32x4 x = pd[v], y = pg[v];
+        n += __popc(nz_bytes(x[0]) & nz_bytes(y[0])) + __popc(nz_bytes(x[1]) & nz_bytes(y[1])) + __popc(nz_bytes(x[2]) & nz_bytes(y[2])) +
+             __popc(nz_bytes(x[3]) & nz_bytes(y[3]));
+    }
+    n = block_sum_int(n, lds4);
+    if (threadIdx.x == 0) {
+        const long long uni = (long long)areas[(size_t)b * (K + G) + k] + areas[(size_t)b * (K + G) + K + g] - n;
+        iou[blockIdx.x] = uni == 0 ? 0.f : (float)((double)n / (double)uni);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// true positive / false positive / ignored
+// ---------------------------------------------------------------------------------------------------------------------------------
+// is candidate (v, ign, g) in front of the kept (bv, bign, bg)?  A total order: higher IoU, then regular before ignored, then lower index
+__device__ inline bool in_front(float v, int ign, int g, float bv, int bign, int bg) {
+    if (g < 0) return false;
+    if (bg < 0) return true;
+    if (v != bv) return v > bv;
+    if (ign != bign) return ign < bign;
+    return g < bg;
+}
+
+// grid B
+__global__ __launch_bounds__(EVAL_THREADS) void eval_match_kernel(const float* __restrict__ iou, const float* __restrict__ ds,
+                                                                 const long long* __restrict__ dl, const int* __restrict__ dc,
+                                                                 const long long* __restrict__ gl, const int* __restrict__ gc,
+                                                                 const unsigned char* __restrict__ ignore, const float* __restrict__ det_area,
+                                                                 const float* __restrict__ gt_area, MatchCfg cfg, int B, int K, int G, int C,
+                                                                 int capacity, const int* __restrict__ cursor, unsigned char* __restrict__ marks,
+                                                                 float* __restrict__ rec_score, int* __restrict__ rec_label,
+                                                                 unsigned char* __restrict__ rec_marks, int* __restrict__ num_gts,
+                                                                 int* __restrict__ overflow) {
+    __shared__ float s_best[EVAL_MAX_K], s_score[EVAL_MAX_K];
+    __shared__ int s_arg[EVAL_MAX_K];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nd = min(max(dc[b], 0), K), ng = min(max(gc[b], 0), G);
+    const unsigned char* ign = ignore ? ignore + (size_t)b * G : nullptr;
+
+    for (int k = wave; k < nd; k += EVAL_THREADS / 64) {
+        const float* row = iou + ((size_t)b * K + k) * G;
+        float bv = -1.f;
+        int bg = -1, bign = 0;
+        for (int g = lane; g < ng; g += 64) {
+            const float v = row[g];
+            if (v < 0.f) continue;                      // another class
+            const int ig = ign && ign[g] ? 1 : 0;
+            if (in_front(v, ig, g, bv, bign, bg)) bv = v, bg = g, bign = ig;
+        }
+        for (int off = 32; off; off >>= 1) {
+            const float ov = __shfl_xor(bv, off);
+            const int og = __shfl_xor(bg, off), oi = __shfl_xor(bign, off);
+            if (in_front(ov, oi, og, bv, bign, bg)) bv = ov, bg = og, bign = oi;
+        }
+        if (lane == 0) s_best[k] = bv, s_arg[k] = bg, s_score[k] = ds[(size_t)b * K + k];
+    }
+    __syncthreads();
+
+    const long long slot = (long long)cursor[0] + b;
+    const bool room = slot >= 0 && slot < capacity;
+    for (int k = tid; k < K; k += EVAL_THREADS) {
+        const bool live = k < nd;
+        float bv = -1.f, sc = 0.f, prev = -1.f, area = 0.f, marea = 0.f;
+        int bg = -1, lab = C;
+        bool mign = false;
+        if (live) {
+            bv = s_best[k], bg = s_arg[k], sc = s_score[k];
+            if (bg >= 0) {
+                for (int j = 0; j < nd; ++j)
+                    if (j != k && s_arg[j] == bg && (s_score[j] > sc || (s_score[j] == sc && j < k))) prev = fmaxf(prev, s_best[j]);
+                mign = ign && ign[bg];
+                marea = gt_area[(size_t)b * G + bg];
+            }
+            area = det_area[(size_t)b * K + k];
+            const long long l = dl[(size_t)b * K + k];
+            lab = l >= 0 && l < C ? (int)l : C;
+        }
+        for (int t = 0; t < cfg.T; ++t)
+            for (int s = 0; s < cfg.S; ++s) {
+                unsigned char m = 0;
+                if (live) {
+                    if (bg < 0 || !(bv >= cfg.thr[t])) m = in_range(cfg, s, area) ? 2 : 0;
+                    else if (mign || !in_range(cfg, s, marea)) m = 0;
+                    else m = prev >= cfg.thr[t] ? 2 : 1;
+                }
+                const size_t ts = (size_t)t * cfg.S + s;
+                marks[(ts * B + b) * K + k] = m;
+                if (room) rec_marks[(ts * capacity + (size_t)slot) * K + k] = m;
+            }
+        if (room) {
+            rec_score[(size_t)slot * K + k] = sc;
+            rec_label[(size_t)slot * K + k] = lab;
+        }
+    }
+    if (room) {
+        for (int g = tid; g < ng; g += EVAL_THREADS) {
+            const long long l = gl[(size_t)b * G + g];
+            if ((ign && ign[g]) || l < 0 || l >= C) continue;
+            const float a = gt_area[(size_t)b * G + g];
+            for (int s = 0; s < cfg.S; ++s)
+                if (in_range(cfg, s, a)) atomicAdd(&num_gts[(size_t)s * C + (int)l], 1);
+        }
+    } else if (tid == 0) {
+        overflow[0] = 1;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// average precision of the sorted segments
+// ---------------------------------------------------------------------------------------------------------------------------------
+// out: inclusive suffix sums over the thread index (Hillis-Steele in LDS); lds[0] is the total.  Ends with a barrier.
+__device__ inline void block_suffix_sum(unsigned v, unsigned* lds) {
+    const int tid = threadIdx.x;
+    lds[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < EVAL_THREADS; off <<= 1) {
+        const unsigned o = tid + off < EVAL_THREADS ? lds[tid + off] : 0u;
+        __syncthreads();
+        lds[tid] += o;
+        __syncthreads();
+    }
+}
+__device__ inline void block_suffix_max(float v, float* lds) {
+    const int tid = threadIdx.x;
+    lds[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < EVAL_THREADS; off <<= 1) {
+        const float o = tid + off < EVAL_THREADS ? lds[tid + off] : 0.f;
+        __syncthreads();
+        lds[tid] = fmaxf(lds[tid], o);
+        __syncthreads();
+    }
+}
+
+// grid T S C; marks: [T S][N] in sorted order, bounds: int [C + 1]
+__global__ __launch_bounds__(EVAL_THREADS) void ap_segments_kernel(const unsigned char* __restrict__ marks, const int* __restrict__ bounds,
+                                                                  const int* __restrict__ num_gts, int S, int C, int N,
+                                                                  float* __restrict__ ap) {
+    __shared__ unsigned s_cnt[EVAL_THREADS];
+    __shared__ float s_max[EVAL_THREADS];
+    __shared__ double s_sum[EVAL_THREADS];
+    __shared__ int lds4[4];
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x % C, ts = blockIdx.x / C, s = ts % S;
+    const int lo = min(max(bounds[c], 0), N), hi = min(max(bounds[c + 1], lo), N);
+    const int ng = num_gts[(size_t)s * C + c];
+    if (ng <= 0 || hi <= lo) {
+        if (tid == 0) ap[blockIdx.x] = 0.f;
+        return;
+    }
+    const unsigned char* m = marks + (size_t)ts * N;
+    const int trips = (hi - lo + AP_CHUNK - 1) / AP_CHUNK;
+
+    int ntp = 0, nfp = 0;
+    for (int trip = 0; trip < trips; ++trip) {
+        const int i0 = lo + trip * AP_CHUNK + tid * AP_PER_THREAD;
+#pragma unroll
+        for (int e = 0; e < AP_PER_THREAD; ++e)
+            if (i0 + e < hi) {
+                const unsigned char v = m[i0 + e];
+                ntp += v == 1;
+                nfp += v == 2;
+            }
+    }
+    const int tot_tp = block_sum_int(ntp, lds4);
+    const int tot_fp = block_sum_int(nfp, lds4);
+
+    const double dng = (double)ng;
+    int after_tp = 0, after_fp = 0;      // marks behind the chunk
+    float run_max = 0.f;                 // the largest precision behind the chunk (and the appended 0)
+    double acc = 0.0;
+    for (int trip = trips - 1; trip >= 0; --trip) {
+        const int i0 = lo + trip * AP_CHUNK + tid * AP_PER_THREAD;
+        unsigned char v[AP_PER_THREAD];
+        unsigned mine = 0;
+#pragma unroll
+        for (int e = 0; e < AP_PER_THREAD; ++e) {
+            v[e] = i0 + e < hi ? m[i0 + e] : (unsigned char)0;
+            mine += (v[e] == 1 ? 1u : 0u) + (v[e] == 2 ? 0x10000u : 0u);
+        }
+        block_suffix_sum(mine, s_cnt);
+        const unsigned behind = tid + 1 < EVAL_THREADS ? s_cnt[tid + 1] : 0u, chunk = s_cnt[0];
+        int tpa = after_tp + (int)(behind & 0xffffu), fpa = after_fp + (int)(behind >> 16);     // marks behind this thread's records
+        float p[AP_PER_THREAD], pmax = 0.f;
+        int tpi[AP_PER_THREAD];
+#pragma unroll
+        for (int e = AP_PER_THREAD - 1; e >= 0; --e) {
+            const int tp = tot_tp - tpa, fp = tot_fp - fpa;                                    // cumulative counts up to and with record e
+            tpi[e] = tp;
+            p[e] = i0 + e < hi ? (float)tp / fmaxf((float)(tp + fp), F32_EPS) : 0.f;
+            pmax = fmaxf(pmax, p[e]);
+            tpa += v[e] == 1;
+            fpa += v[e] == 2;
+        }
+        block_suffix_max(pmax, s_max);
+        float mx = fmaxf(run_max, tid + 1 < EVAL_THREADS ? s_max[tid + 1] : 0.f);
+        const float chunk_max = s_max[0];
+        double term = 0.0;
+#pragma unroll
+        for (int e = AP_PER_THREAD - 1; e >= 0; --e) {
+            mx = fmaxf(mx, p[e]);
+            if (v[e] == 1) term += ((double)tpi[e] / dng - (double)(tpi[e] - 1) / dng) * (double)mx;
+        }
+        s_sum[tid] = term;
+        __syncthreads();
+        for (int off = EVAL_THREADS / 2; off; off >>= 1) {
+            if (tid < off) s_sum[tid] += s_sum[tid + off];
+            __syncthreads();
+        }
+        acc += s_sum[0];
+        after_tp += (int)(chunk & 0xffffu);
+        after_fp += (int)(chunk >> 16);
+        run_max = fmaxf(run_max, chunk_max);
+        __syncthreads();
+    }
+    if (tid == 0) ap[blockIdx.x] = (float)acc;
+}
+
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+inline bool pair_shape_ok(int B, int K, int G) {
+    return B >= 1 && B <= 65535 && K >= 1 && K <= EVAL_MAX_K && G >= 1 && (long long)B * K * G <= 0x7fffffffLL &&
+           (long long)B * (K + G) <= 0x7fffffffLL;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pswin_ap_segments_chunk(void) { return AP_CHUNK; }
+
+int pswin_box_iou_pairs(const float* det_boxes, const long long* det_labels, const int* det_count, const float* gt_boxes,
+                        const long long* gt_labels, const int* gt_count, int B, int K, int G, float* iou, float* det_area, float* gt_area,
+                        void* stream) {
+    PSWIN_CHECK_ARG(det_boxes && det_labels && det_count && gt_boxes && gt_labels && gt_count && iou && pair_shape_ok(B, K, G));
+    PSWIN_CHECK_ARG(aligned16(det_boxes) && aligned16(gt_boxes) && aligned8(det_labels) && aligned8(gt_labels) && aligned4(det_count) &&
+                    aligned4(gt_count) && aligned4(iou) && aligned4(det_area) && aligned4(gt_area));
+    const int total = B * K * G;
+    hipLaunchKernelGGL(box_iou_pairs_kernel, dim3((total + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, (hipStream_t)stream,
+                       det_boxes, det_labels, det_count, gt_boxes, gt_labels, gt_count, K, G, total, iou, det_area, gt_area);
+    PSWIN_LAUNCH_RET();
+}
+
+int pswin_mask_iou_workspace(int B, int K, int G) {
+    PSWIN_CHECK_ARG(pair_shape_ok(B, K, G) && (long long)B * (K + G) * 4 <= 0x7fffffffLL);
+    return B * (K + G) * 4;
+}
+
+int pswin_mask_iou_pairs(const unsigned char* det_masks, const long long* det_labels, const int* det_count, const unsigned char* gt_masks,
+                         const long long* gt_labels, const int* gt_count, int B, int K, int G, int H, int W, float* iou, float* det_area,
+                         float* gt_area, void* workspace, void* stream) {
+    PSWIN_CHECK_ARG(det_masks && det_labels && det_count && gt_masks && gt_labels && gt_count && iou && det_area && gt_area && workspace);
+    PSWIN_CHECK_ARG(pair_shape_ok(B, K, G) && pswin_mask_iou_workspace(B, K, G) > 0 && H >= 1 && W >= 1 &&
+                    (long long)H * W <= 0x7fffffffLL && ((long long)H * W) % 16 == 0);
+    PSWIN_CHECK_ARG(aligned16(det_masks) && aligned16(gt_masks) && aligned8(det_labels) && aligned8(gt_labels) && aligned4(det_count) &&
+                    aligned4(gt_count) && aligned4(iou) && aligned4(det_area) && aligned4(gt_area) && aligned4(workspace));
+    const int vecs = (int)((long long)H * W / 16);
+    int* areas = reinterpret_cast<int*>(workspace);
+    hipLaunchKernelGGL(mask_area_kernel, dim3(B * (K + G)), dim3(EVAL_THREADS), 0, (hipStream_t)stream, det_masks, det_count, gt_masks,
+                       gt_count, K, G, vecs, areas, det_area, gt_area);
+    hipLaunchKernelGGL(mask_pair_kernel, dim3(B * K * G), dim3(EVAL_THREADS), 0, (hipStream_t)stream, det_masks, det_labels, det_count,
+                       gt_masks, gt_labels, gt_count, K, G, vecs, areas, iou);
+    PSWIN_LAUNCH_RET();
+}
+
+int pswin_eval_match(const float* iou, const float* det_scores, const long long* det_labels, const int* det_count, const long long* gt_labels,
+                     const int* gt_count, const unsigned char* ignore, const float* det_area, const float* gt_area, const float* iou_thrs, int T,
+                     const float* area_ranges, int S, int B, int K, int G, int C, int capacity, const int* cursor, unsigned char* marks,
+                     float* rec_score, int* rec_label, unsigned char* rec_marks, int* num_gts, int* overflow, void* stream) {
+    PSWIN_CHECK_ARG(iou && det_scores && det_labels && det_count && gt_labels && gt_count && det_area && gt_area && iou_thrs && cursor &&
+                    marks && rec_score && rec_label && rec_marks && num_gts && overflow);
+    PSWIN_CHECK_ARG(pair_shape_ok(B, K, G) && T >= 1 && T <= EVAL_MAX_T && S >= 1 && S <= EVAL_MAX_S && (area_ranges || S == 1) && C >= 1 &&
+                    C <= 65535 && capacity >= 1);
+    PSWIN_CHECK_ARG((long long)T * S * B * K <= 0x7fffffffLL && (long long)T * S * capacity * K <= 0x7fffffffLL);
+    PSWIN_CHECK_ARG(aligned4(iou) && aligned4(det_scores) && aligned8(det_labels) && aligned8(gt_labels) && aligned4(det_count) &&
+                    aligned4(gt_count) && aligned4(det_area) && aligned4(gt_area) && aligned4(cursor) && aligned4(rec_score) &&
+                    aligned4(rec_label) && aligned4(num_gts) && aligned4(overflow));
+    MatchCfg cfg = {};
+    cfg.T = T, cfg.S = S, cfg.ranged = area_ranges != nullptr;
+    for (int t = 0; t < T; ++t) {
+        PSWIN_CHECK_ARG(iou_thrs[t] > 0.f && iou_thrs[t] <= 1.f);
+        cfg.thr[t] = iou_thrs[t];
+    }
+    for (int s = 0; s < S && area_ranges; ++s) {
+        PSWIN_CHECK_ARG(area_ranges[2 * s] <= area_ranges[2 * s + 1]);       // also rejects NaN
+        cfg.lo[s] = area_ranges[2 * s], cfg.hi[s] = area_ranges[2 * s + 1];
+    }
+    hipLaunchKernelGGL(eval_match_kernel, dim3(B), dim3(EVAL_THREADS), 0, (hipStream_t)stream, iou, det_scores, det_labels, det_count,
+                       gt_labels, gt_count, ignore, det_area, gt_area, cfg, B, K, G, C, capacity, cursor, marks, rec_score, rec_label, rec_marks,
+                       num_gts, overflow);
+    PSWIN_LAUNCH_RET();
+}
+
+int pswin_ap_segments(const unsigned char* marks_sorted, const int* bounds, const int* num_gts, int T, int S, int C, long long N, float* ap,
+                      void* stream) {
+    PSWIN_CHECK_ARG(marks_sorted && bounds && num_gts && ap && aligned4(bounds) && aligned4(num_gts) && aligned4(ap));
+    PSWIN_CHECK_ARG(T >= 1 && T <= EVAL_MAX_T && S >= 1 && S <= EVAL_MAX_S && C >= 1 && C <= 65535 && N >= 1 && N <= (1LL << 24));
+    hipLaunchKernelGGL(ap_segments_kernel, dim3(T * S * C), dim3(EVAL_THREADS), 0, (hipStream_t)stream, marks_sorted, bounds, num_gts, S, C,
+                       (int)N, ap);
+    PSWIN_LAUNCH_RET();
+}
+
+}  // extern "C"

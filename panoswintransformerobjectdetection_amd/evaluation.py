@@ -1,0 +1,463 @@
+"""Mean average precision of the detectors' fixed-shape results: the last step of train -> predict -> score, on the device.
+
+The reference scores a model with mmdet/core/evaluation/mean_ap.py (CustomDataset.evaluate(metric='mAP') -> eval_map): class by class,
+tpfp_default marks every detection of an image as true positive, false positive or ignored, the detections of all images are sorted by
+score, and average_precision(mode='area') integrates the precision / recall curve.  This module states those rules as definitions on
+padded batches (pure torch, any device; pinned to the reference's own results: tests/golden/eval_map.npz, tools/gen_eval_golden.py) and
+runs them on the GPU as HIP kernels that read a Detections and a PaddedTargets in place (csrc/pswin_eval.hip), so that detections never
+leave the device between `heads_predict` and the score:
+
+    acc = MapAccumulator(num_classes=80, iou_thrs=(0.5, 0.75), max_per_img=100, capacity_images=5000, device="cuda")
+    for batch in loader:
+        acc.update(model.simple_test(img), targets)       # no host synchronisation; may be captured with the prediction
+    result = acc.summarize()                              # reads back: mean_ap [T, S], ap [T, S, C], num_gts [S, C], num_dets [C]
+
+THE MATCH IS NOT SEQUENTIAL.  In tpfp_default a detection can only match the box it overlaps most (one argmax over the class's boxes of
+the image, regular boxes first and ignored ones stacked behind them, ties to the first index).  Below the threshold it is a false positive
+(if its own area is inside the area range, when ranges are given); on an ignored box or one outside the range it is neither; otherwise it
+is a true positive exactly when it is the first, in descending score, of the detections that chose this box with an IoU at or above the
+threshold.  `match_pairs` states that, and the marks are pinned EXACTLY: the IoU is bbox_overlaps' float32 expression in its order of
+operations and every comparison is made in float32.
+
+TIES.  The reference leaves equal scores to an unstable argsort.  Here equal scores keep the order (image, row), inside an image and in the
+global order: the choice detector._topk_stable makes, for the same reason (a captured graph, its replays and the definition must agree on
+the bit).  Scores must be positive floats: the global order sorts their bit patterns.
+
+MASKS.  The reference has no mask path (its COCO route needs pycocotools).  The "segm" metric here is this project's choice: the same
+matching rule on the IoU of the full-resolution bitmaps, a pixel counting where its byte is not zero, areas being pixel counts.
+
+Only mode='area' and tpfp_default are in scope; '11points', tpfp_imagenet and proposal recall are not.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import PswinError
+from .detector import Detections, PaddedTargets
+
+MARK_IGNORED, MARK_TP, MARK_FP = 0, 1, 2
+AP_CHUNK = 1024           # records one workgroup of pswin_ap_segments takes per trip (pswin_ap_segments_chunk(); tests aim at it)
+MAX_RECORDS = 1 << 24     # the cumulative counts of a class stay exact in float32, as the reference holds them
+_EPS32 = float(np.finfo(np.float32).eps)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# definitions (any device)
+# ------------------------------------------------------------------------------------------------------------------------
+def box_areas(boxes):
+    """(x2 - x1) (y2 - y1) in float32 of every row of [..., 4]"""
+    b = boxes.float()
+    return (b[..., 2] - b[..., 0]) * (b[..., 3] - b[..., 1])
+
+
+def _pairs(dets, gts):
+    """bool [B, K, Gmax]: detection inside its count, box inside its count, one class"""
+    K, G = dets.labels.shape[1], gts.labels.shape[1]
+    dev = dets.labels.device
+    dk = torch.arange(K, device=dev)[None, :] < dets.count[:, None]
+    gk = torch.arange(G, device=dev)[None, :] < gts.count[:, None]
+    return dk[:, :, None] & gk[:, None, :] & (dets.labels[:, :, None] == gts.labels[:, None, :])
+
+
+def box_iou_pairs(dets, gts):
+    """f32 [B, K, Gmax]: bbox_overlaps' float32 expression overlap / max(area_d + area_g - overlap, 1e-6) for the pairs with
+    k < dets.count[b], g < gts.count[b] and equal labels, -1 for every other pair."""
+    d, g = dets.boxes.float()[:, :, None, :], gts.boxes.float()[:, None, :, :]
+    a1, a2 = box_areas(dets.boxes)[:, :, None], box_areas(gts.boxes)[:, None, :]
+    xs, ys = torch.maximum(d[..., 0], g[..., 0]), torch.maximum(d[..., 1], g[..., 1])
+    xe, ye = torch.minimum(d[..., 2], g[..., 2]), torch.minimum(d[..., 3], g[..., 3])
+    overlap = (xe - xs).clamp(min=0) * (ye - ys).clamp(min=0)
+    union = (a1 + a2 - overlap).clamp(min=1e-6)
+    return torch.where(_pairs(dets, gts), overlap / union, torch.full_like(overlap, -1.0))
+
+
+def mask_areas(dets, gts):
+    """(f32 [B, K], f32 [B, Gmax]): the number of non-zero bytes of every mask inside its count, 0 past it"""
+    def one(masks, count):
+        n = (masks != 0).flatten(2).sum(2)
+        inside = torch.arange(masks.shape[1], device=masks.device)[None, :] < count[:, None]
+        return torch.where(inside, n, torch.zeros_like(n)).float()
+    return one(dets.masks, dets.count), one(gts.masks, gts.count)
+
+
+def mask_iou_pairs(dets, gts):
+    """f32 [B, K, Gmax], the layout of box_iou_pairs, for dets.masks uint8 [B, K, H, W] and gts.masks uint8 [B, Gmax, H, W]: a pixel counts
+    where its byte is non-zero; inter and both areas are exact integers; float32(double(inter) / double(union)), 0 when the union is 0."""
+    d, g = (dets.masks != 0).flatten(2), (gts.masks != 0).flatten(2)
+    dt = torch.float32 if d.shape[2] < (1 << 24) else torch.float64            # sums of 0 / 1 below 2^24: exact in float32
+    inter = torch.matmul(d.to(dt), g.to(dt).transpose(1, 2)).double()
+    union = d.sum(2).double()[:, :, None] + g.sum(2).double()[:, None, :] - inter
+    iou = torch.where(union == 0, torch.zeros_like(inter), inter / union.clamp(min=1)).float()
+    return torch.where(_pairs(dets, gts), iou, torch.full_like(iou, -1.0))
+
+
+def _ranges(area_ranges, device):
+    """None, or (min f32 [S], max f32 [S])"""
+    if area_ranges is None:
+        return None
+    r = torch.tensor([[float(a), float(b)] for a, b in area_ranges], dtype=torch.float32, device=device)
+    return r[:, 0], r[:, 1]
+
+
+def match_pairs(iou, dets, gts, ignore, iou_thrs, area_ranges, det_area, gt_area):
+    """tpfp_default on a padded batch: uint8 [T, S, B, K] of 0 (ignored, or past the count), 1 (true positive), 2 (false positive).
+    iou f32 [B, K, Gmax] as box_iou_pairs / mask_iou_pairs return it (a negative entry is no candidate); ignore bool [B, Gmax] or None --
+    on an argmax tie regular boxes come before ignored ones, then the lower index wins; iou_thrs: floats in (0, 1], compared as float32;
+    area_ranges: None or (min_area, max_area) pairs (the reference's scale_ranges squared), compared as float32 with det_area f32 [B, K]
+    and gt_area f32 [B, Gmax].  Equal scores: the lower row is in front.  Reads the counts back (a definition, not for a captured step)."""
+    B, K, G = iou.shape
+    dev = iou.device
+    T, S = len(iou_thrs), 1 if area_ranges is None else len(area_ranges)
+    thr = torch.tensor([float(t) for t in iou_thrs], dtype=torch.float32, device=dev)
+    rng = _ranges(area_ranges, dev)
+    marks = torch.zeros(T, S, B, K, dtype=torch.uint8, device=dev)
+    for b, (nd, ng) in enumerate(zip(dets.count.tolist(), gts.count.tolist())):
+        nd, ng = max(0, min(nd, K)), max(0, min(ng, G))
+        if nd == 0:
+            continue
+        best = torch.full((nd,), -1.0, device=dev)
+        arg = torch.zeros(nd, dtype=torch.long, device=dev)
+        ign = torch.zeros(max(ng, 1), dtype=torch.bool, device=dev)
+        if ng:
+            if ignore is not None:
+                ign = ignore[b, :ng].bool()
+            perm = torch.sort(ign.long(), stable=True)[1]                  # regular boxes first, each group in ascending index
+            v = iou[b, :nd, :ng][:, perm]
+            best, first = v.max(1)[0], v.argmax(1)                         # argmax: the first of equal maxima
+            arg = perm[first]
+        has = best >= 0
+        sc = dets.scores[b, :nd]
+        rows = torch.arange(nd, device=dev)
+        front = (sc[:, None] > sc[None, :]) | ((sc[:, None] == sc[None, :]) & (rows[:, None] < rows[None, :]))     # [j, k]: j before k
+        same = (arg[:, None] == arg[None, :]) & has[:, None] & has[None, :]
+        prev = torch.where(front & same, best[:, None].expand(nd, nd), torch.full((nd, nd), -1.0, device=dev)).max(0)[0]
+        m_ign = ign[arg] & has
+        for t in range(T):
+            below = ~has | ~(best >= thr[t])
+            for s in range(S):
+                d_in = torch.ones(nd, dtype=torch.bool, device=dev)
+                m_in = d_in
+                if rng is not None:
+                    da, ga = det_area[b, :nd], gt_area[b, arg.clamp(max=G - 1)]
+                    d_in, m_in = (da >= rng[0][s]) & (da < rng[1][s]), (ga >= rng[0][s]) & (ga < rng[1][s])
+                matched = torch.where(m_ign | ~m_in, 0, torch.where(prev >= thr[t], MARK_FP, MARK_TP))
+                marks[t, s, b, :nd] = torch.where(below, torch.where(d_in, MARK_FP, 0), matched).to(torch.uint8)
+    return marks
+
+
+def count_gts(gts, ignore, gt_area, area_ranges, num_classes):
+    """int32 [B, S, C]: the regular boxes of every image per (range, class) -- the reference's num_gts, image by image"""
+    B, G = gts.labels.shape
+    dev = gts.labels.device
+    ok = (torch.arange(G, device=dev)[None, :] < gts.count[:, None]) & (gts.labels >= 0) & (gts.labels < num_classes)
+    if ignore is not None:
+        ok = ok & ~ignore.bool()
+    rng = _ranges(area_ranges, dev)
+    inr = ok[:, None, :] if rng is None else ok[:, None, :] & (gt_area[:, None, :] >= rng[0][None, :, None]) & \
+        (gt_area[:, None, :] < rng[1][None, :, None])
+    onehot = gts.labels.clamp(0, num_classes - 1)[:, :, None] == torch.arange(num_classes, device=dev)[None, None, :]
+    return (inr[:, :, :, None] & onehot[:, None, :, :]).sum(2).to(torch.int32)
+
+
+def precision_recall_sorted(marks, num_gts):
+    """(recall f64 [n], precision f32 [n]) of marks uint8 [n] in sorted order, as eval_map computes them: integer cumulative counts,
+    recall = tp / max(num_gts, eps) in float64, precision = float32(tp / max(tp + fp, eps))."""
+    tp, fp = (marks == MARK_TP).cumsum(0), (marks == MARK_FP).cumsum(0)
+    precision = tp.float() / (tp + fp).float().clamp(min=_EPS32)
+    return tp.double() / max(float(num_gts), _EPS32), precision
+
+
+def average_precision_sorted(marks, num_gts):
+    """average_precision(mode='area') on marks uint8 [n] in sorted order: 0-dim f32.  The curve of precision_recall_sorted with (0, 0) in
+    front and (1, 0) behind, precision made monotone from the right, the sum of (recall step) x precision where recall changes, in
+    float64, rounded to float32.  num_gts == 0 gives 0."""
+    if int(num_gts) == 0 or marks.numel() == 0:
+        return torch.zeros((), dtype=torch.float32, device=marks.device)
+    recall, precision = precision_recall_sorted(marks, num_gts)
+    z, one = recall.new_zeros(1), recall.new_ones(1)
+    mrec, mpre = torch.cat([z, recall, one]), torch.cat([z, precision.double(), z])
+    mpre = torch.cummax(mpre.flip(0), 0)[0].flip(0)
+    ind = torch.nonzero(mrec[1:] != mrec[:-1])[:, 0]
+    return ((mrec[ind + 1] - mrec[ind]) * mpre[ind + 1]).sum().float()
+
+
+def ap_segments(marks_sorted, bounds, num_gts):
+    """f32 [T, S, C]: average_precision_sorted of every (threshold, range, class).  marks_sorted uint8 [T, S, N] in the global order
+    (class, descending score, slot, row), bounds int [C + 1] (class c owns records bounds[c] .. bounds[c + 1] - 1), num_gts int [S, C]."""
+    T, S = marks_sorted.shape[:2]
+    C = bounds.numel() - 1
+    bd, ng = bounds.tolist(), num_gts.tolist()
+    ap = torch.zeros(T, S, C, dtype=torch.float32, device=marks_sorted.device)
+    for t in range(T):
+        for s in range(S):
+            for c in range(C):
+                ap[t, s, c] = average_precision_sorted(marks_sorted[t, s, bd[c]:bd[c + 1]], ng[s][c])
+    return ap
+
+
+def sort_records(scores, labels, num_classes):
+    """The global order of records (score f32 [N] positive, label int32 [N] with num_classes for "no record"): (order long [N], bounds
+    int32 [C + 1]).  A stable sort of the int64 key label << 32 | (0x7fffffff - the score's bit pattern): class, then descending score,
+    then the position (slot, row)."""
+    key = (labels.long() << 32) | (0x7FFFFFFF - scores.contiguous().view(torch.int32).long())
+    order = torch.sort(key, stable=True)[1]
+    bounds = torch.searchsorted(labels[order].contiguous(), torch.arange(num_classes + 1, dtype=labels.dtype, device=labels.device))
+    return order, bounds.to(torch.int32)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the list form: the reference's eval_map on its own arguments
+# ------------------------------------------------------------------------------------------------------------------------
+def padded_from_lists(det_results, annotations, num_classes=None):
+    """(Detections, PaddedTargets, ignore bool [B, Gmax], num_classes) on the CPU from eval_map's arguments: det_results per image either
+    a list of per-class [n, 5] arrays (x1, y1, x2, y2, score) or what Detections.as_lists() gives, (dets [k, 5], labels [k], masks);
+    annotations per image a dict of bboxes [n, 4], labels [n] and optionally bboxes_ignore, labels_ignore.  Rows keep their order (class
+    by class for the per-class form); ignored boxes follow the regular ones, as tpfp_default stacks them."""
+    rows = []
+    for res in det_results:
+        if isinstance(res, tuple) and len(res) == 3 and torch.is_tensor(res[0]):
+            if num_classes is None:
+                raise PswinError("padded_from_lists: the Detections.as_lists() form needs num_classes")
+            rows.append((res[0].detach().cpu().float().reshape(-1, 5), res[1].detach().cpu().long().reshape(-1)))
+        else:
+            num_classes = len(res) if num_classes is None else num_classes
+            d = [torch.as_tensor(np.asarray(a, dtype=np.float32)).reshape(-1, 5) for a in res]
+            rows.append((torch.cat(d), torch.cat([torch.full((a.shape[0],), c, dtype=torch.long) for c, a in enumerate(d)])))
+    B, K = len(rows), max(1, max(r[0].shape[0] for r in rows))
+    dets = Detections(torch.zeros(B, K, 4), torch.zeros(B, K), torch.zeros(B, K, dtype=torch.long),
+                      torch.tensor([r[0].shape[0] for r in rows], dtype=torch.int32), torch.zeros(B, K, dtype=torch.int32))
+    for b, (d, l) in enumerate(rows):
+        dets.boxes[b, :len(l)], dets.scores[b, :len(l)], dets.labels[b, :len(l)] = d[:, :4], d[:, 4], l
+    gl = []
+    for ann in annotations:
+        bx = torch.as_tensor(np.asarray(ann["bboxes"], dtype=np.float32)).reshape(-1, 4)
+        lb = torch.as_tensor(np.asarray(ann["labels"])).long().reshape(-1)
+        ig = torch.zeros(lb.shape[0], dtype=torch.bool)
+        if ann.get("labels_ignore", None) is not None:
+            bi = torch.as_tensor(np.asarray(ann["bboxes_ignore"], dtype=np.float32)).reshape(-1, 4)
+            li = torch.as_tensor(np.asarray(ann["labels_ignore"])).long().reshape(-1)
+            bx, lb, ig = torch.cat([bx, bi]), torch.cat([lb, li]), torch.cat([ig, torch.ones(li.shape[0], dtype=torch.bool)])
+        gl.append((bx, lb, ig))
+    G = max(1, max(g[1].shape[0] for g in gl))
+    gts = PaddedTargets(torch.zeros(B, G, 4), torch.zeros(B, G, dtype=torch.long), torch.tensor([g[1].shape[0] for g in gl], dtype=torch.int32))
+    ignore = torch.zeros(B, G, dtype=torch.bool)
+    for b, (bx, lb, ig) in enumerate(gl):
+        gts.boxes[b, :len(lb)], gts.labels[b, :len(lb)], ignore[b, :len(lb)] = bx, lb, ig
+    return dets, gts, ignore, num_classes
+
+
+def eval_map_lists(det_results, annotations, scale_ranges=None, iou_thr=0.5, num_classes=None):
+    """The reference's eval_map(det_results, annotations, scale_ranges, iou_thr) from the definitions above, with its return value:
+    (mean_ap, [dict(num_gts, num_dets, recall, precision, ap) per class]) -- scalars without scale_ranges, one entry per range with
+    them.  det_results may also be what Detections.as_lists() produces (then num_classes is required)."""
+    dets, gts, ignore, C = padded_from_lists(det_results, annotations, num_classes)
+    area_ranges = None if scale_ranges is None else [(r[0] ** 2, r[1] ** 2) for r in scale_ranges]
+    S = 1 if area_ranges is None else len(area_ranges)
+    det_area, gt_area = box_areas(dets.boxes), box_areas(gts.boxes)
+    marks = match_pairs(box_iou_pairs(dets, gts), dets, gts, ignore, (iou_thr,), area_ranges, det_area, gt_area)[0]     # [S, B, K]
+    num_gts = count_gts(gts, ignore, gt_area, area_ranges, C).sum(0)                                                      # [S, C]
+    live = torch.arange(dets.labels.shape[1])[None, :] < dets.count[:, None]
+    results = []
+    for c in range(C):
+        sel = (live & (dets.labels == c)).reshape(-1)
+        order = torch.sort(dets.scores.reshape(-1)[sel], descending=True, stable=True)[1]
+        rec, pre, ap = [], [], []
+        for s in range(S):
+            m = marks[s].reshape(-1)[sel][order]
+            r, p = precision_recall_sorted(m, int(num_gts[s, c]))
+            rec.append(r.numpy()), pre.append(p.numpy()), ap.append(average_precision_sorted(m, int(num_gts[s, c])).numpy())
+        if scale_ranges is None:
+            results.append(dict(num_gts=int(num_gts[0, c]), num_dets=int(sel.sum()), recall=rec[0], precision=pre[0], ap=ap[0][()]))
+        else:
+            results.append(dict(num_gts=num_gts[:, c].numpy().astype(int), num_dets=int(sel.sum()), recall=np.stack(rec),
+                                precision=np.stack(pre), ap=np.stack(ap)))
+    aps = np.array([[np.float64(np.reshape(r["ap"], -1)[s]) for r in results] for s in range(S)]).reshape(S, C)
+    has = num_gts.numpy() > 0
+    mean_ap = [float(aps[s][has[s]].mean()) if has[s].any() else 0.0 for s in range(S)]
+    return (mean_ap[0] if scale_ranges is None else mean_ap), results
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the kernels (csrc/pswin_eval.hip) and the dispatch: on CPU tensors every step runs the definitions
+# ------------------------------------------------------------------------------------------------------------------------
+def _floats(values):
+    return (ctypes.c_float * len(values))(*[float(v) for v in values])
+
+
+def _check_batch(dets, gts):
+    B, K = dets.labels.shape
+    if gts.labels.shape[0] != B:
+        raise PswinError(f"evaluation: {B} images of detections, {gts.labels.shape[0]} of targets")
+    for name, t, dt in (("dets.boxes", dets.boxes, torch.float32), ("dets.scores", dets.scores, torch.float32),
+                        ("dets.labels", dets.labels, torch.int64), ("dets.count", dets.count, torch.int32),
+                        ("targets.boxes", gts.boxes, torch.float32), ("targets.labels", gts.labels, torch.int64),
+                        ("targets.count", gts.count, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dets.labels.device:
+            raise PswinError(f"evaluation: {name} must be a contiguous {dt} tensor on {dets.labels.device}")
+
+
+def _check_masks(dets, gts):
+    if dets.masks is None or gts.masks is None:
+        raise PswinError("evaluation: the mask metric needs dets.masks and targets.masks")
+    if dets.masks.shape[2:] != gts.masks.shape[2:] or dets.masks.dtype != torch.uint8 or gts.masks.dtype != torch.uint8:
+        raise PswinError(f"evaluation: masks must be uint8 of one size, got {tuple(dets.masks.shape)} {dets.masks.dtype} and "
+                         f"{tuple(gts.masks.shape)} {gts.masks.dtype}")
+
+
+def _out(out, shape, dtype, device, what):
+    """`out` after a check of its shape, or a fresh buffer"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise PswinError(f"{what}: out must be a contiguous {dtype} tensor {tuple(shape)} on {device}")
+    return out
+
+
+def pair_iou_dispatch(dets, gts, iou="bbox", out=None):
+    """(iou f32 [B, K, Gmax], det_area f32 [B, K], gt_area f32 [B, Gmax]) of the box or the mask metric.  On the GPU: pswin_box_iou_pairs
+    or pswin_mask_iou_pairs, into the three buffers of `out` if given; on the CPU the definitions."""
+    _check_batch(dets, gts)
+    if iou == "segm":
+        _check_masks(dets, gts)
+    elif iou != "bbox":
+        raise PswinError(f"evaluation: iou must be 'bbox' or 'segm', got {iou!r}")
+    if not dets.labels.is_cuda:
+        if iou == "segm":
+            return (mask_iou_pairs(dets, gts),) + mask_areas(dets, gts)
+        return box_iou_pairs(dets, gts), box_areas(dets.boxes), box_areas(gts.boxes)
+    (B, K), G = dets.labels.shape, gts.labels.shape[1]
+    dev, bufs = dets.labels.device, out or (None, None, None)
+    out = _out(bufs[0], (B, K, G), torch.float32, dev, "pair_iou_dispatch")
+    det_area, gt_area = _out(bufs[1], (B, K), torch.float32, dev, "pair_iou_dispatch"), _out(bufs[2], (B, G), torch.float32, dev, "pair_iou_dispatch")
+    p = _lib.ptr
+    if iou == "segm":
+        dm, gm = dets.masks.contiguous(), gts.masks.contiguous()
+        H, W = dm.shape[2:]
+        n = _lib.load().pswin_mask_iou_workspace(B, K, G)
+        _lib.check(min(n, 0), "pswin_mask_iou_workspace")
+        ws = torch.empty(n, dtype=torch.uint8, device=out.device)
+        pairs = B * K * G                                  # an upper bound of the bytes read: every pair of one class inside the counts
+        _lib.call("pswin_mask_iou_pairs", out, p(dm), p(dets.labels), p(dets.count), p(gm), p(gts.labels), p(gts.count), B, K, G, H, W, p(out),
+                  p(det_area), p(gt_area), p(ws), algo_bytes=(B * (K + G) + 2 * pairs) * H * W)
+    else:
+        _lib.call("pswin_box_iou_pairs", out, p(dets.boxes), p(dets.labels), p(dets.count), p(gts.boxes), p(gts.labels), p(gts.count), B, K, G,
+                  p(out), p(det_area), p(gt_area), algo_bytes=B * (K + G) * 24 + B * K * G * 4)
+    return out, det_area, gt_area
+
+
+def _flags(ignore, gts):
+    if ignore is None:
+        return None
+    if ignore.shape != gts.labels.shape or ignore.dtype not in (torch.bool, torch.uint8) or ignore.device != gts.labels.device:
+        raise PswinError(f"evaluation: ignore must be bool {tuple(gts.labels.shape)} on {gts.labels.device}")
+    return ignore.contiguous()
+
+
+def ap_segments_dispatch(marks_sorted, bounds, num_gts, out=None):
+    """ap_segments.  On the GPU one launch, a workgroup per (threshold, range, class) (pswin_ap_segments), into `out` if given; on the CPU
+    the definition."""
+    if not marks_sorted.is_cuda:
+        return ap_segments(marks_sorted, bounds, num_gts)
+    T, S, N = marks_sorted.shape
+    C = bounds.numel() - 1
+    marks_sorted, bounds, num_gts = marks_sorted.contiguous(), bounds.to(torch.int32).contiguous(), num_gts.to(torch.int32).contiguous()
+    if tuple(num_gts.shape) != (S, C) or marks_sorted.dtype != torch.uint8:
+        raise PswinError(f"ap_segments: marks uint8 [T, S, N], bounds [C + 1], num_gts [S, C]; got {tuple(marks_sorted.shape)}, "
+                         f"{tuple(bounds.shape)}, {tuple(num_gts.shape)}")
+    ap = _out(out, (T, S, C), torch.float32, marks_sorted.device, "ap_segments_dispatch")
+    _lib.call("pswin_ap_segments", ap, _lib.ptr(marks_sorted), _lib.ptr(bounds), _lib.ptr(num_gts), T, S, C, N, _lib.ptr(ap),
+              algo_bytes=2 * T * S * N)
+    return ap
+
+
+class MapAccumulator:
+    """mAP over a data set, batch by batch, in buffers of a fixed shape on `device`.  iou_thrs: T thresholds; scale_ranges: None or S
+    pairs as the reference's eval_map takes them (their squares bound the areas); capacity_images: the image slots; max_per_img: K, the
+    rows of a Detections; iou: "bbox" or "segm".
+
+    A record is a detection row's score f32, label int32 and its T x S marks; image `cursor + b` of all updates owns rows
+    [slot K, slot K + K) of rec_score / rec_label [capacity, K] and rec_marks [T, S, capacity, K].  An unused row carries label C."""
+
+    def __init__(self, num_classes, iou_thrs=(0.5,), scale_ranges=None, capacity_images=1024, max_per_img=100, iou="bbox", device="cpu"):
+        self.C, self.K, self.capacity, self.iou = int(num_classes), int(max_per_img), int(capacity_images), iou
+        self.iou_thrs = tuple(float(t) for t in iou_thrs)
+        self.area_ranges = None if scale_ranges is None else tuple((float(r[0]) ** 2, float(r[1]) ** 2) for r in scale_ranges)
+        self.T, self.S = len(self.iou_thrs), 1 if scale_ranges is None else len(scale_ranges)
+        if iou not in ("bbox", "segm"):
+            raise PswinError(f"MapAccumulator: iou must be 'bbox' or 'segm', got {iou!r}")
+        if not (self.C >= 1 and self.K >= 1 and self.capacity >= 1 and 1 <= self.T <= 16 and 1 <= self.S <= 8):
+            raise PswinError("MapAccumulator: num_classes, max_per_img, capacity_images >= 1, 1 to 16 thresholds, 1 to 8 ranges")
+        if any(not 0 < t <= 1 for t in self.iou_thrs):
+            raise PswinError(f"MapAccumulator: thresholds must lie in (0, 1], got {self.iou_thrs}")
+        if self.capacity * self.K > MAX_RECORDS:
+            raise PswinError(f"MapAccumulator: capacity_images x max_per_img must not exceed {MAX_RECORDS} records")
+        dev = torch.device(device)
+        self.rec_score = torch.zeros(self.capacity, self.K, device=dev)
+        self.rec_label = torch.full((self.capacity, self.K), self.C, dtype=torch.int32, device=dev)
+        self.rec_marks = torch.zeros(self.T, self.S, self.capacity, self.K, dtype=torch.uint8, device=dev)
+        self.num_gts = torch.zeros(self.S, self.C, dtype=torch.int32, device=dev)
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def reset(self):
+        """Forget every record, in place (stream-ordered; the buffers keep their addresses for a captured update)."""
+        self.rec_score.zero_(), self.rec_marks.zero_(), self.num_gts.zero_(), self.cursor.zero_(), self.overflow.zero_()
+        self.rec_label.fill_(self.C)
+        return self
+
+    def update(self, dets, targets, ignore=None, out=None):
+        """Score one batch: marks uint8 [T, S, B, K], and the batch's records appended at the cursor, which advances by B.  dets: a
+        Detections with K = max_per_img rows; targets: a PaddedTargets, or the list form, padded on entry (PaddedTargets.of: the one
+        host read, of the lists' box counts); ignore: bool [B, Gmax] or None.  No host synchronisation and no data-dependent shape: it
+        can be captured with the prediction.  An image without detections and boxes contributes nothing, so a short last batch is padded
+        with such images.  Image slots at or past the capacity are not written; summarize() raises then.  out: the GPU path's buffer for
+        the marks, if the caller keeps one."""
+        gts = PaddedTargets.of(targets)
+        B, K = dets.labels.shape
+        if K != self.K or dets.labels.device != self.cursor.device:
+            raise PswinError(f"MapAccumulator.update: detections [{B}, {K}] on {dets.labels.device}, the accumulator holds max_per_img = "
+                             f"{self.K} on {self.cursor.device}")
+        ignore = _flags(ignore, gts)
+        iou, det_area, gt_area = pair_iou_dispatch(dets, gts, self.iou)
+        G = gts.labels.shape[1]
+        if not iou.is_cuda:
+            marks = match_pairs(iou, dets, gts, ignore, self.iou_thrs, self.area_ranges, det_area, gt_area)
+            per_image = count_gts(gts, ignore, gt_area, self.area_ranges, self.C)
+            live = torch.arange(K)[None, :] < dets.count[:, None]
+            label = torch.where(live & (dets.labels >= 0) & (dets.labels < self.C), dets.labels, self.C).to(torch.int32)
+            score = torch.where(live, dets.scores, torch.zeros_like(dets.scores))
+            for b in range(B):
+                slot = int(self.cursor) + b
+                if slot >= self.capacity:
+                    self.overflow.fill_(1)
+                    continue
+                self.rec_score[slot], self.rec_label[slot], self.rec_marks[:, :, slot] = score[b], label[b], marks[:, :, b]
+                self.num_gts += per_image[b]
+        else:
+            marks = _out(out, (self.T, self.S, B, K), torch.uint8, iou.device, "MapAccumulator.update")
+            p = _lib.ptr
+            ranges = None if self.area_ranges is None else _floats([v for r in self.area_ranges for v in r])
+            _lib.call("pswin_eval_match", iou, p(iou), p(dets.scores), p(dets.labels), p(dets.count), p(gts.labels), p(gts.count), p(ignore),
+                      p(det_area), p(gt_area), _floats(self.iou_thrs), self.T, ranges, self.S, B, K, G, self.C, self.capacity, p(self.cursor),
+                      p(marks), p(self.rec_score), p(self.rec_label), p(self.rec_marks), p(self.num_gts), p(self.overflow),
+                      algo_bytes=B * K * G * 4 + 2 * self.T * self.S * B * K + B * K * 24)
+        self.cursor.add_(B)
+        return marks
+
+    def summarize(self):
+        """Reads back: dict(mean_ap f32 [T, S], ap f32 [T, S, C], num_gts int32 [S, C], num_dets int32 [C]) on the CPU.  mean_ap is the mean
+        over the classes with num_gts > 0, or 0.0 if there are none, as the reference reports it."""
+        if int(self.overflow):
+            raise PswinError(f"MapAccumulator: more than capacity_images = {self.capacity} images were given; the records past it are lost")
+        order, bounds = sort_records(self.rec_score.reshape(-1), self.rec_label.reshape(-1), self.C)
+        marks_sorted = self.rec_marks.reshape(self.T, self.S, -1).index_select(2, order)
+        ap = ap_segments_dispatch(marks_sorted, bounds, self.num_gts).cpu()
+        num_gts, bounds = self.num_gts.cpu(), bounds.cpu()
+        has = num_gts > 0
+        mean_ap = torch.zeros(self.T, self.S)
+        for s in range(self.S):
+            if has[s].any():
+                mean_ap[:, s] = ap[:, s, has[s]].double().mean(1).float()
+        return dict(mean_ap=mean_ap, ap=ap, num_gts=num_gts, num_dets=bounds[1:] - bounds[:-1])
