@@ -7,8 +7,12 @@
 //   roi * spatial_scale - 0.5; bins of (roi_h / P) x (roi_w / P); per bin an ADAPTIVE grid of ceil(roi_h / P) x ceil(roi_w / P)
 //   samples (sampling_ratio = 0) at the sub-bin centres; a sample outside [-1, H] x [-1, W] contributes 0, otherwise the
 //   coordinate is clamped to [0, H-1] and read bilinearly; the bin is the mean over the grid.
-// PARITY: unpinned against the reference (no mmcv.ops source or fixture in the tree); tests check it against a plain PyTorch
-// statement of the same definition.
+// PARITY: unpinned against mmcv's binary (no mmcv.ops source or fixture in the tree).  Pinned is the definition above: bit for bit
+// against its float64 evaluation on exactly summable operands (dyadic geometry, power-of-two sample counts, integer features and
+// gradients; tests/test_roi_exact_gpu.py, cases in tests/_roi_cases.py) for every (dtype, C) instantiation of both kernels, both
+// paths of the backward at footprints of 16 and 17 cells, samples exactly on -1 and on H, aligned = 0 and a clamped roi_level; inside
+// counted roundings where 1 / count is rounded; and on random boxes against a float32 PyTorch statement (tests/test_roi_gpu.py).
+// The two NMS kernels below equal the sequential rule on integer boxes with IoUs exactly on the threshold (same files).
 //
 // Layout: feature maps NHWC (a pixel's C channels are one contiguous 512-byte row for C = 256 bf16), output [R, P, P, C].
 // Forward: one wave per (RoI, bin); a pixel row is read by C / VEC lanes with 16-byte loads, the 64 / (C / VEC) lane groups of the
@@ -17,7 +21,7 @@
 // Backward: the adjoint scatter with f32 atomics, one per touched cell of a bin (separable weights), (one dword per lane, 64 consecutive channels per wave instruction = the 256
 // contiguous bytes the memory-side atomic units take at full rate; MI355X_MICROARCH.md, Global float atomics) into f32 NHWC
 // gradient maps that the caller zeroes.  Sums over RoIs therefore depend on arrival order (as torch's grid_sample backward,
-// which this replaces): not bitwise reproducible from run to run.
+// which this replaces): not bitwise reproducible from run to run, unless every partial sum is exact (the exact tests' operands).
 #include "pswin_common.hpp"
 
 using namespace pswin;
