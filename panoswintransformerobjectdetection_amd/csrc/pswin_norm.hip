@@ -11,6 +11,9 @@
 // Mapping: a row of C elements is L lanes x up to 4 chunks of 4 elements (L = 2..64, a power of two, chosen on
 // the host so that L * 16 >= C); consecutive lanes read consecutive 16-byte chunks; row reductions are log2(L)
 // __shfl_xor steps.  Statistics and all arithmetic are fp32 regardless of the I/O dtype.
+// Pinned by tests/test_ln_edges_gpu.py: every output within a float64 bound counted from the roundings below (tests/_ln_cases.py);
+// y from the stored statistics, every bf16 store (round to nearest even) and the sums of integer gradients bit for bit.
+// Not pinned: the order of the additions inside a row sum, and rsqrtf beyond its documented accuracy.
 #include "pswin_common.hpp"
 
 using namespace pswin;
