@@ -109,10 +109,12 @@ constexpr unsigned ES = (DT == PSWIN_F32) ? 4u : 2u;
 // request would put the wait for the load right behind it) ...
 template <int DT>
 using raw4_t = std::conditional_t<DT == PSWIN_F32, f32x4, u32x2>;
-template <int DT>
+// AUX: the cache policy bits of the buffer instruction (0 = default, NT = non-temporal: a stream the kernel reads once)
+constexpr int NT = 2;
+template <int DT, int AUX = 0>
 __device__ inline raw4_t<DT> braw4(rsrc_t r, unsigned boff) {
-    if constexpr (DT == PSWIN_F32) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, boff, 0, 0));
-    else return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, boff, 0, 0));
+    if constexpr (DT == PSWIN_F32) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, boff, 0, AUX));
+    else return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, boff, 0, AUX));
 }
 // ... and as f32 (the bf16 expansion is load4's)
 template <int DT>
@@ -128,14 +130,14 @@ __device__ inline f32x4 expand4(raw4_t<DT> raw) {
         return v;
     }
 }
-template <int DT>
-__device__ inline f32x4 bload4(rsrc_t r, unsigned boff) { return expand4<DT>(braw4<DT>(r, boff)); }
-template <int DT>
+template <int DT, int AUX = 0>
+__device__ inline f32x4 bload4(rsrc_t r, unsigned boff) { return expand4<DT>(braw4<DT, AUX>(r, boff)); }
+template <int DT, int AUX = 0>
 __device__ inline void bstore4(rsrc_t r, unsigned boff, f32x4 v) {
     if constexpr (DT == PSWIN_F32) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, boff, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, boff, 0, AUX);
     } else {
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])}, r, boff, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])}, r, boff, 0, AUX);
     }
 }
 __device__ inline unsigned bload_u32(rsrc_t r, unsigned boff) { return __builtin_amdgcn_raw_buffer_load_b32(r, boff, 0, 0); }
@@ -458,7 +460,7 @@ __global__ __launch_bounds__(THREADS, (EX && NCH == 3) ? 4 : 1) void ln_bwd_kern
                                                          const float* __restrict__ res_scale, float* __restrict__ part,
                                                          long long rows, int C, BwdExtra ex = BwdExtra{}) {
     constexpr int RPB = THREADS / L;
-    __shared__ float red[2][THREADS * 4];      // [row group][lane][4 elements] of one chunk column at a time
+    __shared__ alignas(16) float red[2][THREADS * 4];      // [row group][lane][4 elements] of one chunk column at a time
     const int lane = threadIdx.x % L;
     const int rsub = threadIdx.x / L;
     const int nchunks = C / 4;
@@ -561,17 +563,17 @@ __device__ inline void bwd_partials(float (&red)[2][THREADS * 4], const f32x4 (&
             }
         }
         __syncthreads();
-        if (rsub == 0 && ch < nchunks) {
+        if (rsub == 0 && ch < nchunks) {            // the four elements of a chunk side by side (one 16-byte LDS read each), every sum in row-group order
+            f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+            for (int q = 0; q < RPB; ++q) {
+                a = a + *reinterpret_cast<const f32x4*>(&red[0][(q * L + lane) * 4]);
+                c = c + *reinterpret_cast<const f32x4*>(&red[1][(q * L + lane) * 4]);
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float a = 0.f, c = 0.f;
-#pragma unroll 4
-                for (int q = 0; q < RPB; ++q) {
-                    a += red[0][(q * L + lane) * 4 + e];
-                    c += red[1][(q * L + lane) * 4 + e];
-                }
-                outp[4 * ch + e] = a;
-                outp[C + 4 * ch + e] = c;
+                outp[4 * ch + e] = a[e];
+                outp[C + 4 * ch + e] = c[e];
             }
         }
         if constexpr (RSUM) {
@@ -582,13 +584,11 @@ __device__ inline void bwd_partials(float (&red)[2][THREADS * 4], const f32x4 (&
             }
             __syncthreads();
             if (rsub == 0 && ch < nchunks) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float a = 0.f;
+                f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
-                    for (int q = 0; q < RPB; ++q) a += red[0][(q * L + lane) * 4 + e];
-                    outp[2 * C + 4 * ch + e] = a;
-                }
+                for (int q = 0; q < RPB; ++q) a = a + *reinterpret_cast<const f32x4*>(&red[0][(q * L + lane) * 4]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) outp[2 * C + 4 * ch + e] = a[e];
             }
         }
     }
@@ -597,7 +597,8 @@ __device__ inline void bwd_partials(float (&red)[2][THREADS * 4], const f32x4 (&
 // The exact-row form of ln_bwd_kernel, MODE 0, fp32 x (C == 12 * L): the same persistent grid, partial rows and arithmetic, as a
 // software pipeline one row deep.  When dx of row i is in registers, the operands of row i + 1 (x, dres, dy, mean, rstd, the scales)
 // are requested -- before row i's stores, which the single in-order counter would otherwise put in front of them -- and inv[] of row
-// i + 2 behind them.  A prefetch past the last row reads zeros through OOB.
+// i + 2 behind them.  A prefetch past the last row reads zeros through OOB.  x, dres and dy are read once and carry the non-temporal
+// policy; dx and the extra output are read by the next kernel and keep the default one.
 struct BwdRow {               // what a row needs besides its chunks: requested with them
     unsigned em;                // ex.map[r]
     float mu, rs_, rsc, exsc;
@@ -610,7 +611,7 @@ __global__ __launch_bounds__(THREADS, 4) void ln_bwd_rows_kernel(const void* __r
                                                                  const float* __restrict__ res_scale, float* __restrict__ part,
                                                                  unsigned rows, unsigned B, BwdExtra ex) {
     constexpr int NCH = 3, C = 4 * L * NCH, RPB = THREADS / L;
-    __shared__ float red[2][THREADS * 4];
+    __shared__ alignas(16) float red[2][THREADS * 4];
     const unsigned lane = threadIdx.x % L, rsub = threadIdx.x / L;
     const unsigned S = (unsigned)rs.S, n_out = (unsigned)rs.n_out, n_ex = (unsigned)ex.n_rows;
     const bool has_inv = inv != nullptr, has_dres = dres != nullptr, has_rsc = RSUM && res_scale != nullptr;
@@ -638,6 +639,7 @@ __global__ __launch_bounds__(THREADS, 4) void ln_bwd_rows_kernel(const void* __r
         unsigned row, b, r;
         bool ok;
     };
+    const unsigned step = gridDim.x * RPB;
     auto pos_of = [&](unsigned row0) {
         const unsigned b0 = row0 / S, r0 = row0 - b0 * S + rsub;
         const bool wrap = r0 >= S;
@@ -656,21 +658,24 @@ __global__ __launch_bounds__(THREADS, 4) void ln_bwd_rows_kernel(const void* __r
         const unsigned dyo = p.ok ? (p.b * n_out + (has_inv ? iv : p.r)) * (C * ES<DYDT>) + lane * (4 * ES<DYDT>) : OOB;
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {             // OOB + the chunk offsets stays past every operand
-            xv[k] = bload4<PSWIN_F32>(xr, xo + k * L * 16u);
-            rv[k] = bload4<PSWIN_F32>(drr, xo + k * L * 16u);
-            dyv[k] = braw4<DYDT>(dyr, dyo + k * L * (4 * ES<DYDT>));
+            xv[k] = bload4<PSWIN_F32, NT>(xr, xo + k * L * 16u);
+            rv[k] = bload4<PSWIN_F32, NT>(drr, xo + k * L * 16u);
+            dyv[k] = braw4<DYDT, NT>(dyr, dyo + k * L * (4 * ES<DYDT>));
         }
     };
 
-    const unsigned stride = gridDim.x * RPB;
     unsigned row0 = blockIdx.x * RPB;
-    Pos pc = pos_of(row0), pn = pos_of(row0 + stride);
+    Pos pc = pos_of(row0), pn = pos_of(row0 + step);
     BwdRow cur;
     f32x4 xv[NCH], rv[NCH];
     raw4_t<DYDT> dyv[NCH];
-    fetch_row(pc, fetch_idx(pc), cur, xv, rv, dyv);
+    const unsigned iv_first = fetch_idx(pc);
+    __builtin_amdgcn_sched_barrier(0);
+    fetch_row(pc, iv_first, cur, xv, rv, dyv);
     unsigned iv_next = fetch_idx(pn);
-    for (; row0 < rows; row0 += stride) {
+    __builtin_amdgcn_sched_barrier(0);
+    // one trip: the math of the row in registers, the request for the next one, the stores
+    auto trip = [&](unsigned row0) {
         const float mu = cur.mu, rs_ = cur.rs_;
         f32x4 xh[NCH], g[NCH], rc[NCH];
         float s1 = 0.f, s2 = 0.f;
@@ -699,7 +704,7 @@ __global__ __launch_bounds__(THREADS, 4) void ln_bwd_rows_kernel(const void* __r
         __builtin_amdgcn_sched_barrier(0);          // not earlier: hoisted above the row math, the request no longer fits in 128 VGPRs
         fetch_row(pn, iv_next, cur, xv, rv, dyv);
         pc = pn;
-        pn = pos_of(row0 + 2 * stride);
+        pn = pos_of(row0 + 2 * step);
         iv_next = fetch_idx(pn);
         __builtin_amdgcn_sched_barrier(0);          // and not later: behind the stores it would wait for them
 #pragma unroll
@@ -707,9 +712,25 @@ __global__ __launch_bounds__(THREADS, 4) void ln_bwd_rows_kernel(const void* __r
             bstore4<PSWIN_F32>(dxr, dx_off + k * L * 16u, v[k]);
             if constexpr (EX) bstore4<PSWIN_BF16>(exr, ex_off + k * L * 8u, v[k] * ex_sc);
         }
+    };
+    // Dropped stores (OOB), as many as a trip makes, and a loop that is entered without a test (a workgroup owns at least one trip): both
+    // edges then reach the loop header with the same requests outstanding -- the next row, the index behind it, a row's stores -- and
+    // the first waits of a trip are counted ones that leave the previous row's stores in flight.  With a test in front of the loop the
+    // compiler moves the first request behind it and behind these stores, and the header wait drains everything again.
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        bstore4<PSWIN_F32>(dxr, OOB + k * L * 16u, f32x4{0.f, 0.f, 0.f, 0.f});
+        if constexpr (EX) bstore4<PSWIN_BF16>(exr, OOB + k * L * 8u, f32x4{0.f, 0.f, 0.f, 0.f});
     }
-    if constexpr (EX) bwd_zero_pads<L, NCH>(ex, (int)lane, (int)rsub, NCH * L, C);
-    bwd_partials<L, NCH, RSUM>(red, dg, db, dr, part, (int)lane, (int)rsub, NCH * L, C);
+    __builtin_amdgcn_sched_barrier(0);
+    do {
+        trip(row0);
+        row0 += step;
+    } while (row0 < rows);
+    unsigned le = lane, re = rsub;
+    asm volatile("" : "+v"(le), "+v"(re));          // the addresses of the ends are worked out here, not carried through the loop
+    if constexpr (EX) bwd_zero_pads<L, NCH>(ex, (int)le, (int)re, NCH * L, C);
+    bwd_partials<L, NCH, RSUM>(red, dg, db, dr, part, (int)le, (int)re, NCH * L, C);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -792,7 +813,7 @@ __global__ __launch_bounds__(THREADS) void ln_nchw_bwd_kernel(const float* __res
     constexpr int RPB = THREADS / L;
     constexpr int Q = RPB / 4;
     extern __shared__ float tile[];                 // [RPB][C + 4] then the partial-sum staging
-    __shared__ float red[2][THREADS * 4];
+    __shared__ alignas(16) float red[2][THREADS * 4];
     const int lane = threadIdx.x % L, rsub = threadIdx.x / L;
     const int nchunks = C / 4, LD = C + 4;
     f32x4 dg[NCH], db[NCH];
@@ -916,7 +937,7 @@ __global__ __launch_bounds__(THREADS, 4) void ln_nchw_bwd_rows_kernel(const floa
     constexpr int TIT = C * Q / THREADS;            // 16-byte requests per thread for a dy tile (= 3)
     static_assert(C * Q % THREADS == 0, "the dy tile is a whole number of requests per thread");
     extern __shared__ float tile[];                 // [RPB][C + 4]
-    __shared__ float red[2][THREADS * 4];
+    __shared__ alignas(16) float red[2][THREADS * 4];
     const unsigned lane = threadIdx.x % L, rsub = threadIdx.x / L;
     const bool has_dres = dres != nullptr, has_exs = ex != nullptr && ex_scale != nullptr;
     const rsrc_t dyr = uniform_rsrc(dy, rows * (C * 4u)), xr = uniform_rsrc(x, rows * (C * 4u)), drr = uniform_rsrc(dres, rows * (C * 4u));
@@ -932,27 +953,29 @@ __global__ __launch_bounds__(THREADS, 4) void ln_nchw_bwd_rows_kernel(const floa
     }
     f32x4 tq[TIT], xv[NCH], rv[NCH];
     float mu, rs_, exs;
+    const unsigned step = gridDim.x * RPB;
     auto fetch = [&](unsigned row0) {
         const bool ok = row0 < rows;                // block-uniform (S % RPB == 0)
         const unsigned b = row0 / S, t0 = row0 - b * S, row = row0 + rsub;
 #pragma unroll
         for (int it = 0; it < TIT; ++it) {
             const unsigned i = threadIdx.x + it * THREADS, c = i / Q, r4 = i - c * Q;
-            tq[it] = bload4<PSWIN_F32>(dyr, ok ? ((b * C + c) * S + t0 + 4 * r4) * 4u : OOB);
+            tq[it] = bload4<PSWIN_F32, NT>(dyr, ok ? ((b * C + c) * S + t0 + 4 * r4) * 4u : OOB);
         }
         mu = bload_f32(meanr, ok ? row * 4u : OOB);
         rs_ = bload_f32(rstdr, ok ? row * 4u : OOB);
         exs = bload_f32(exsr, ok ? b * 4u : OOB);
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {
-            xv[k] = bload4<PSWIN_F32>(xr, ok ? row * (C * 4u) + (lane + k * L) * 16u : OOB);
-            rv[k] = bload4<PSWIN_F32>(drr, ok ? row * (C * 4u) + (lane + k * L) * 16u : OOB);
+            xv[k] = bload4<PSWIN_F32, NT>(xr, ok ? row * (C * 4u) + (lane + k * L) * 16u : OOB);
+            rv[k] = bload4<PSWIN_F32, NT>(drr, ok ? row * (C * 4u) + (lane + k * L) * 16u : OOB);
         }
     };
-    const unsigned stride = gridDim.x * RPB;
     unsigned row0 = blockIdx.x * RPB;
+    __builtin_amdgcn_sched_barrier(0);
     fetch(row0);
-    for (; row0 < rows; row0 += stride) {
+    __builtin_amdgcn_sched_barrier(0);
+    auto trip = [&](unsigned row0) {
         const unsigned row = row0 + rsub;
         __syncthreads();
 #pragma unroll
@@ -962,7 +985,9 @@ __global__ __launch_bounds__(THREADS, 4) void ln_nchw_bwd_rows_kernel(const floa
             for (int e = 0; e < 4; ++e) tile[(4 * r4 + e) * LD + c] = tq[it][e];
         }
         __syncthreads();
-        const float mu_ = mu, rs0 = rs_, es = exs;
+        // a value of its own, not the register the next trip's ex_scale[b] is loaded into: a copy of that one at the end of the trip
+        // would wait for the request just made
+        const float mu_ = mu, rs0 = rs_, es = has_exs ? exs : 1.0f;
         f32x4 xh[NCH], g[NCH], v[NCH];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -978,15 +1003,26 @@ __global__ __launch_bounds__(THREADS, 4) void ln_nchw_bwd_rows_kernel(const floa
             v[k] = has_dres ? v[k] + rv[k] : v[k];
         }
         __builtin_amdgcn_sched_barrier(0);          // the request stays between the row math and the stores (see ln_bwd_rows_kernel)
-        fetch(row0 + stride);
+        fetch(row0 + step);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {
             bstore4<PSWIN_F32>(dxr, row * (C * 4u) + (lane + k * L) * 16u, v[k]);
             // ex: bf16(scale[b] * dx) in token order (see ln_nchw_bwd_kernel); ex == nullptr: a zero-byte resource drops the store
-            bstore4<PSWIN_BF16>(exr, row * (C * 2u) + (lane + k * L) * 8u, has_exs ? v[k] * es : v[k]);
+            bstore4<PSWIN_BF16>(exr, row * (C * 2u) + (lane + k * L) * 8u, v[k] * es);
         }
+    };
+    // dropped stores and a loop entered without a test: the loop header sees the same requests on both edges (see ln_bwd_rows_kernel)
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        bstore4<PSWIN_F32>(dxr, OOB + k * L * 16u, f32x4{0.f, 0.f, 0.f, 0.f});
+        bstore4<PSWIN_BF16>(exr, OOB + k * L * 8u, f32x4{0.f, 0.f, 0.f, 0.f});
     }
+    __builtin_amdgcn_sched_barrier(0);
+    do {
+        trip(row0);
+        row0 += step;
+    } while (row0 < rows);
     bwd_partials<L, NCH, false>(red, dg, db, no_dr, part, (int)lane, (int)rsub, NCH * L, C);
 }
 
