@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSWIN_ABI_VERSION 7
+#define PSWIN_ABI_VERSION 8
 
 #define PSWIN_F32 0
 #define PSWIN_BF16 1
@@ -769,6 +769,29 @@ int pswin_pano_resize_normalize_pad(const uint8_t* src, const int32_t* out_hw, c
  * [0, w1-1], cw to [1, w1-cx].  src, norm, dst, to_rgb: as pswin_pano_resize_normalize_pad. */
 int pswin_pano_resize_crop_resize_normalize_pad(const uint8_t* src, const int32_t* plan, const float* norm, int to_rgb, float* dst, int B,
                                                 int H, int W, int Hp, int Wp, void* stream);
+
+/* The instance masks of a batch through the geometry of the two launches above, into PaddedTargets.masks, in one launch:
+ *   dst[b][r][y][x] = 0 for r >= count[b] (clamped to [0, Gmax]), for y >= oh and for x >= ow; otherwise
+ *   dst[b][r][y][x] = max over k in {0, 1} with 0 <= a = rows[b][r][k] < Gin of Wm[b][a][sy][sx]    (no such k: 0), where
+ *   nn(d, n_in, n_out) = min((int)floor(d * (1.0 / ((double)n_out / (double)n_in))), n_in - 1) in float64, uncontracted: the index rule
+ *     of cv2.resize(INTER_NEAREST), which mmdet's BitmapMasks.rescale / resize reach through mmcv.imrescale(interpolation='nearest').
+ *     PARITY: unpinned -- neither cv2 nor mmcv is at hand to compare with;
+ *   h1 <= 0: sy = nn(y, H, oh), sx = nn(x, W, ow);
+ *   h1 >  0: iy = cy + nn(y, ch, oh), ix = cx + nn(x, cw, ow), sy = nn(iy, H, h1), sx = nn(ix, W, w1);
+ *   Wm[b][a] = the plane (src[b][a] != 0), values 0 / 1, through pswin_pano_warp_u8 with params[b] as a one-channel image: on such a
+ *     plane the half-up rounding of the stretch's blend is "blend + 0.5 >= 1" and the result is again 0 / 1.  The reference has no
+ *     mask path for PanoStretch and RollAug; the mask goes where the image goes, by the same expression.
+ * rows[b][r] names the one or two source rows output row r came from (second entry -1: one source; RollAug's seam merge joins two):
+ * pano_aug.py, "Row provenance".  Entries outside [0, Gin) read nothing.
+ * src: uint8 [B, Gin, H, W]; params: f64 [B, 4] as pswin_pano_warp_u8; plan: int32 [B, 8] as
+ * pswin_pano_resize_crop_resize_normalize_pad and clamped alike; rows: int32 [B, Gmax, 2]; count: int32 [B]; dst: uint8
+ * [B, Gmax, Hp, Wp], distinct from src.  All on the DEVICE (a captured graph replays with whatever the buffers hold).  EVERY byte of dst
+ * is written, by vector stores (16 bytes per lane where Wp % 16 == 0 and dst is 16-byte aligned, 4 where Wp % 4 == 0, bytes
+ * otherwise): no memset, no atomics, no dependence on what dst held.  No intermediate mask is stored; the geometry of a pixel is worked
+ * out once and reused for the Gmax rows, and without the stretch flag no trigonometric function runs.  H >= 2, W even, any positive
+ * Hp, Wp; H * W and Hp * Wp below 2^31 (offsets inside a plane are 32-bit, plane bases 64-bit), B <= 65535, Hp <= 16 * 65535. */
+int pswin_pano_masks(const uint8_t* src, const double* params, const int32_t* plan, const int32_t* rows, const int32_t* count, uint8_t* dst,
+                     int B, int Gin, int Gmax, int H, int W, int Hp, int Wp, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Detector inference behind the heads (csrc/pswin_detect.hip; panoswintransformerobjectdetection_amd/detector.py:

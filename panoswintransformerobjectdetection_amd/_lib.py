@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PSWIN_LIB") or os.path.join(_PKG, "libpswin_hip.so") 
 F32, BF16 = 0, 1
 MODE_PLANAR, MODE_PANO = 0, 1
 WS, WTOK, WPAD, HEAD_DIM = 7, 49, 64, 32
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -171,6 +171,7 @@ _PROTOTYPES = {
     "pswin_pano_warp_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "pswin_pano_resize_normalize_pad": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "pswin_pano_resize_crop_resize_normalize_pad": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "pswin_pano_masks": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 // Panorama training augmentation on the device: PanoStretch + RollAug + RandomFlip in one gather (pswin_pano_warp_u8),
 // Resize + Normalize + Pad into the backbone's input in a second one (pswin_pano_resize_normalize_pad), and the Resize -> RandomCrop ->
-// Resize policy of the recipe's AutoAugment in the place of that resize (pswin_pano_resize_crop_resize_normalize_pad).
+// Resize policy of the recipe's AutoAugment in the place of that resize (pswin_pano_resize_crop_resize_normalize_pad).  The instance
+// masks of the batch take the same geometry in one more gather, straight into the detector's padded target buffer (pswin_pano_masks).
 //
 // Reference: PanoStretch / RollAug (mmdet/datasets/pipelines/transforms.py:992-1068) call lzx/yolo/extensions/xzaug.py getAug,
 // which resamples with scipy.ndimage.map_coordinates(order=1, mode='wrap') on float64 coordinates, and rollaug.py roll_aug_raw
@@ -366,6 +367,192 @@ __global__ __launch_bounds__(PANO_TX* PANO_TY) void pano_rcr_kernel(const unsign
     if (y < Hp && x < Wp) store_planes(dst, b, y, x, Hp, Wp, vec, out);
 }
 
+// ---- Instance masks through the same geometry, into PaddedTargets.masks (pswin_pano_masks) ---------------------------------------
+//
+// One gather per output byte: dst[b][r][y][x] = max over the one or two source rows a of rows[b][r] of Wm[a][sy][sx], where (sy, sx) is
+// the nearest-neighbour chain of the plan and Wm[a] the 0 / 1 plane src[b][a] != 0 through the image's warp.  Nothing but dst is
+// written.  The geometry does not depend on r, so a thread works it out once for its MASK_PX consecutive columns of one output row
+// and keeps it in registers while it walks the Gmax rows:
+//   without the stretch  one byte offset into the source plane per pixel;
+//   with the stretch     the offset of the top-left tap and a 16-entry table in 16 bits.  On a 0 / 1 plane the blend
+//                        0.0 + v00*wy0*wx0 + v01*wy0*wx1 + v10*wy1*wx0 + v11*wy1*wx1 of pano_warp_kernel has 16 possible values, one
+//                        per combination of the four taps; (int)(t + 0.5) of each is bit (v00 | v01 << 1 | v10 << 2 | v11 << 3) of
+//                        the table.  The second taps sit 0 or 1 column and 0 or 1 row further (taps()): bits 16 and 17.
+// So the trig runs once per pixel (per column and per row where it factors, through LDS as in pano_warp_kernel), never per row of the
+// row map, and not at all for an image without the stretch flag.
+constexpr int MASK_TX = 16;                      // threads along x; each owns MASK_PX consecutive output columns
+constexpr int MASK_TY = 16;                      // output rows per workgroup, one per thread row
+constexpr int MASK_PX = 16;                      // one 16-byte store per thread and row of the row map
+constexpr int MASK_COLS = MASK_TX * MASK_PX;     // 256 output columns per workgroup
+
+// cv2.resize(INTER_NEAREST): source index of output index d for n_in -> n_out, float64, uncontracted.
+__device__ inline int nn_index(int d, int n_in, int n_out) {
+    const double inv = 1.0 / ((double)n_out / (double)n_in);
+    const double f = floor((double)d * inv);
+    return f < (double)(n_in - 1) ? (int)f : n_in - 1;
+}
+
+// 16 bytes of one output row at column x (a multiple of 16).  mode 2: rows are 16-byte aligned and Wp % 16 == 0, one 128-bit store;
+// mode 1: rows are 4-byte aligned and Wp % 4 == 0, one 32-bit store per four columns inside the row; mode 0: bytes.
+__device__ inline void store_mask16(unsigned char* __restrict__ row, int x, int Wp, int mode, const unsigned int (&w)[4]) {
+    if (mode == 2) {
+        *reinterpret_cast<u32x4*>(row + x) = u32x4{w[0], w[1], w[2], w[3]};
+    } else if (mode == 1) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (x + 4 * k < Wp) *reinterpret_cast<unsigned int*>(row + x + 4 * k) = w[k];
+    } else {
+#pragma unroll
+        for (int j = 0; j < MASK_PX; ++j)
+            if (x + j < Wp) row[x + j] = (unsigned char)((w[j >> 2] >> (8 * (j & 3))) & 255u);
+    }
+}
+
+// grid (ceil(Wp / 256), ceil(Hp / 16), B), block (16, 16).  No thread returns before the barrier.
+__global__ __launch_bounds__(MASK_TX* MASK_TY) void pano_masks_kernel(const unsigned char* __restrict__ src, const double* __restrict__ params,
+                                                                       const int32_t* __restrict__ plan, const int32_t* __restrict__ rows,
+                                                                       const int32_t* __restrict__ count, unsigned char* __restrict__ dst,
+                                                                       int Gin, int Gmax, int H, int W, int Hp, int Wp, int mode) {
+    __shared__ int s_xs[MASK_COLS], s_xd[MASK_COLS], s_sy[MASK_TY];
+    __shared__ double s_wx0[MASK_COLS], s_wx1[MASK_COLS], s_su0[MASK_COLS], s_su[MASK_COLS];
+    __shared__ double s_tanv[MASK_TY];
+    const int b = blockIdx.z;
+    const double kx = params[4 * b + 0], ky = params[4 * b + 1];
+    double sh = fmod(params[4 * b + 2], (double)W);        // as pano_warp_kernel
+    sh = sh == sh ? (sh < 0.0 ? sh + (double)W : sh) : 0.0;
+    const int shift = sh >= 0.0 && sh < (double)W ? (int)sh : 0;
+    const int flags = (int)params[4 * b + 3];
+    const bool stretch = (flags & 1) != 0, flip = (flags & 2) != 0;
+    const int32_t* p = plan + 8 * b;
+    const int h1 = p[0] < 1 ? 0 : p[0];                    // 0: the plain resize H x W -> oh x ow
+    const int oh = clampi(p[6], 0, Hp), ow = clampi(p[7], 0, Wp);
+    const int hc = h1 < 1 ? 1 : h1, w1 = p[1] < 1 ? 1 : p[1];      // the clamps of pano_rcr_kernel; unused where h1 == 0
+    const int cy = clampi(p[2], 0, hc - 1), cx = clampi(p[3], 0, w1 - 1);
+    const int ch = clampi(p[4], 1, hc - cy), cw = clampi(p[5], 1, w1 - cx);
+    const int tid = threadIdx.y * MASK_TX + threadIdx.x;
+    const int xblk = blockIdx.x * MASK_COLS, yblk = blockIdx.y * MASK_TY;
+
+    // per-column table (one column per thread): the column of the stretched image this output column shows, and its horizontal taps
+    {
+        const int x = xblk + tid;
+        if (x < ow) {
+            const int sx = h1 <= 0 ? nn_index(x, W, ow) : nn_index(cx + nn_index(x, cw, ow), W, w1);
+            int xs = (flip ? W - 1 - sx : sx) - shift;
+            xs = xs < 0 ? xs + W : xs;
+            if (stretch) {
+                const double u = (((double)xs + 0.5) / (double)W - 0.5) * 2.0 * PANO_PI;
+                const double su = sin(u), cu = cos(u);
+                const double u0 = atan2(su * kx / ky, cu);
+                const double refx = (u0 / (2.0 * PANO_PI) + 0.5) * (double)W - 0.5;
+                int xa, xb;
+                double w0, w1_;
+                taps(refx, W, xa, xb, w0, w1_);
+                s_xs[tid] = xa;
+                s_xd[tid] = xb - xa;
+                s_wx0[tid] = w0;
+                s_wx1[tid] = w1_;
+                s_su0[tid] = sin(u0);
+                s_su[tid] = su;
+            } else {
+                s_xs[tid] = xs;
+            }
+        }
+        if (tid < MASK_TY && yblk + tid < oh) {
+            const int y = yblk + tid;
+            const int sy = h1 <= 0 ? nn_index(y, H, oh) : nn_index(cy + nn_index(y, ch, oh), H, h1);
+            s_sy[tid] = sy;
+            if (stretch) {
+                const double v = (((double)sy + 0.5) / (double)H - 0.5) * PANO_PI;
+                s_tanv[tid] = tan(v);
+            }
+        }
+    }
+    __syncthreads();
+
+    const int y = yblk + threadIdx.y;
+    const int xl = threadIdx.x * MASK_PX;
+    const int x = xblk + xl;
+    if (y >= Hp || x >= Wp) return;
+    // columns x .. x + nvalid - 1 of this row lie inside oh x ow; everything else is the pad
+    const int nvalid = y < oh ? clampi(ow - x, 0, MASK_PX) : 0;
+    int off[MASK_PX];
+    unsigned int lut[MASK_PX];
+    if (nvalid > 0) {
+        const int sy = s_sy[threadIdx.y];
+        if (stretch) {
+            const double tv = s_tanv[threadIdx.y];
+#pragma unroll
+            for (int j = 0; j < MASK_PX; ++j) {
+                const int col = j < nvalid ? xl + j : xl;
+                const double v0 = atan(tv * s_su0[col] / s_su[col] * ky);
+                const double refy = (v0 / PANO_PI + 0.5) * (double)H - 0.5;
+                int ya, yb;
+                double wy0, wy1;
+                taps(refy, H, ya, yb, wy0, wy1);
+                const double p00 = 1.0 * wy0 * s_wx0[col], p01 = 1.0 * wy0 * s_wx1[col];
+                const double p10 = 1.0 * wy1 * s_wx0[col], p11 = 1.0 * wy1 * s_wx1[col];
+                unsigned int t16 = 0;
+#pragma unroll
+                for (int m = 1; m < 16; ++m) {
+                    double t = 0.0 + ((m & 1) ? p00 : 0.0);
+                    t = t + ((m & 2) ? p01 : 0.0);
+                    t = t + ((m & 4) ? p10 : 0.0);
+                    t = t + ((m & 8) ? p11 : 0.0);
+                    t16 |= (unsigned int)(round_u8(t) != 0) << m;
+                }
+                off[j] = ya * W + s_xs[col];
+                lut[j] = j < nvalid ? (t16 | (unsigned int)s_xd[col] << 16 | (unsigned int)(yb - ya) << 17) : 0u;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < MASK_PX; ++j) off[j] = sy * W + s_xs[j < nvalid ? xl + j : xl];
+        }
+    }
+
+    int cnt = count[b];
+    cnt = cnt < 0 ? 0 : (cnt > Gmax ? Gmax : cnt);
+    const size_t plane = (size_t)H * W, oplane = (size_t)Hp * Wp;
+    const unsigned char* img = src + (size_t)b * Gin * plane;
+    unsigned char* out = dst + (size_t)b * Gmax * oplane + (size_t)y * Wp;
+    // 0x01 in every byte of the 16 that lies inside oh x ow: the loads below are unconditional (a column past ow reads the thread's
+    // first pixel again, which is in bounds) and the words are masked once
+    unsigned int inside[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int n = clampi(nvalid - 4 * k, 0, 4);
+        inside[k] = n == 4 ? 0x01010101u : ((1u << (8 * n)) - 1u) & 0x01010101u;
+    }
+    // one source plane's contribution to the 16 bytes
+    auto gather = [&](const unsigned char* __restrict__ pl, unsigned int (&w)[4]) {
+        if (stretch) {
+#pragma unroll
+            for (int j = 0; j < MASK_PX; ++j) {
+                const int dx = (int)((lut[j] >> 16) & 1u), dy = (lut[j] >> 17) & 1u ? W : 0;
+                const unsigned char* q = pl + off[j];
+                const unsigned int m = (unsigned int)(q[0] != 0) | (unsigned int)(q[dx] != 0) << 1 | (unsigned int)(q[dy] != 0) << 2 |
+                                       (unsigned int)(q[dy + dx] != 0) << 3;
+                w[j >> 2] |= ((lut[j] >> m) & 1u) << (8 * (j & 3));
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < MASK_PX; ++j) w[j >> 2] |= (unsigned int)(pl[off[j]] != 0) << (8 * (j & 3));
+        }
+    };
+    const int32_t* rmap = rows + (size_t)b * Gmax * 2;
+#pragma unroll 2
+    for (int g = 0; g < Gmax; ++g) {
+        unsigned int w[4] = {0u, 0u, 0u, 0u};
+        if (g < cnt && nvalid > 0) {
+            const int a0 = rmap[2 * g], a1 = rmap[2 * g + 1];     // -1: no second source; anything else outside [0, Gin) reads nothing
+            if (a0 >= 0 && a0 < Gin) gather(img + (size_t)a0 * plane, w);
+            if (a1 >= 0 && a1 < Gin) gather(img + (size_t)a1 * plane, w);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) w[k] &= inside[k];
+        }
+        store_mask16(out + (size_t)g * oplane, x, Wp, mode, w);
+    }
+}
+
 template <int C>
 void launch_warp(const uint8_t* src, uint8_t* dst, const double* params, int B, int H, int W, int vec, hipStream_t st) {
     dim3 grid((W + PANO_COLS - 1) / PANO_COLS, (H + WARP_ROWS - 1) / WARP_ROWS, B);
@@ -386,6 +573,21 @@ extern "C" int pswin_pano_warp_u8(const uint8_t* src, const double* params, uint
         case 3: launch_warp<3>(src, dst, params, B, H, W, vec, st); break;
         default: launch_warp<4>(src, dst, params, B, H, W, vec, st); break;
     }
+    PSWIN_LAUNCH_RET();
+}
+
+extern "C" int pswin_pano_masks(const uint8_t* src, const double* params, const int32_t* plan, const int32_t* rows, const int32_t* count,
+                                uint8_t* dst, int B, int Gin, int Gmax, int H, int W, int Hp, int Wp, void* stream) {
+    PSWIN_CHECK_ARG(src != nullptr && params != nullptr && plan != nullptr && rows != nullptr && count != nullptr && dst != nullptr);
+    PSWIN_CHECK_ARG(src != dst && B > 0 && B <= 65535 && Gin > 0 && Gmax > 0 && H >= 2 && W >= 2 && W % 2 == 0 && Hp > 0 && Wp > 0);
+    // offsets inside one plane are 32-bit, plane bases 64-bit
+    PSWIN_CHECK_ARG((long long)H * W <= 0x7fffffffLL && (long long)Hp * Wp <= 0x7fffffffLL);
+    PSWIN_CHECK_ARG((long long)B * Gmax <= 0x7fffffffLL && (long long)B * Gin <= 0x7fffffffLL);
+    PSWIN_CHECK_ARG((Hp + MASK_TY - 1) / MASK_TY <= 65535);
+    const int mode = (Wp % 16 == 0 && ((uintptr_t)dst & 15) == 0) ? 2 : ((Wp % 4 == 0 && ((uintptr_t)dst & 3) == 0) ? 1 : 0);
+    dim3 grid((Wp + MASK_COLS - 1) / MASK_COLS, (Hp + MASK_TY - 1) / MASK_TY, B);
+    hipLaunchKernelGGL(pano_masks_kernel, grid, dim3(MASK_TX, MASK_TY), 0, (hipStream_t)stream, src, params, plan, rows, count, dst, Gin,
+                       Gmax, H, W, Hp, Wp, mode);
     PSWIN_LAUNCH_RET();
 }
 

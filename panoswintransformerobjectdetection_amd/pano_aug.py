@@ -57,6 +57,27 @@ nothing.  Pixels: pswin_pano_resize_crop_resize_normalize_pad does both resizes 
 image is never stored), so the uint8 stages may differ from cv2 by 1 LSB twice.  Boxes: resize_boxes -> crop_boxes (float32 subtract,
 clip to the crop, keep x2 > x1 and y2 > y1; an empty result is valid) -> resize_boxes on the crop's size.  pano_ratio_v is
 [y1 / h1, y2 / h1] of the crop (transforms.py:874, PanoCheck 1128-1132), [0.0, 1.0] without one.
+
+Row provenance (row_map= of transform_one, transform_boxes, crop_boxes, auto_augment_boxes): boxes change rows on the way, and whatever
+is attached to a box (its instance mask) must follow.  A map is int32 [n_out, 2]: the input rows output row r came from, the second
+entry -1 where there is one source.  An unpaired row maps to itself.  A row the seam merge emits maps to (j, left[-1]): j the right row that
+is emitted, left[-1] the last left partner in _roll_rows' iteration order, the row whose x2 the emitted row shows.  crop_boxes selects
+the rows of the map it is given; auto_augment_boxes(row_map=transform_one's map) returns the composition, which is what
+pswin_pano_masks takes.
+
+Instance masks (transform_masks_one is the definition, warp_resize_masks the launch, PanoTrainTransform.with_targets the entry): every
+Mask R-CNN config of the reference sends gt_masks (BitmapMasks) through RandomFlip -> AutoAugment -> Pad; there Resize is
+mmcv.imrescale / imresize(interpolation='nearest') per bitmap, RandomCrop a slice, Pad zeros.  Here one launch writes
+PaddedTargets.masks: output pixel (y, x) of row r shows pixel (sy, sx) of the warped source planes of the row map, with
+nn(d, n_in, n_out) = min(int(floor(d * (1 / (n_out / n_in)))), n_in - 1) in float64 along each axis -- the index rule of
+cv2.resize(INTER_NEAREST) -- chained through resize, crop offset and resize.  PARITY: unpinned -- neither cv2 nor mmcv is installed
+next to this project or shipped in the reference tree, so the rule is stated from cv2's source, not compared with it; the fixture
+tests/golden/pano_masks.npz pins order, row keeping, crop arithmetic and sizes to the reference, with this rule standing in for
+mmcv's resampling.  PanoStretch and RollAug have NO mask path in the reference.  The project's choice: the mask goes where the image
+goes, by the same expression -- the 0 / 1 plane `mask != 0` through the image's warp as a one-channel image (float64 coordinates, the
+wrap quirk, the taps, half-up rounding, then roll, then flip).  On a 0 / 1 plane that rounding is "blend + 0.5 >= 1", so the result is
+again 0 / 1, and pano_warp on a [n, H, W, 1] batch states the same planes independently.  A merged seam pair shows the OR of its two
+pieces.
 """
 import numpy as np
 import torch
@@ -347,9 +368,14 @@ def _stretch_corners(pts, H, W, kx, ky):
     return np.stack([(u / (2 * np.pi) + 0.5) * W - 0.5, (v / np.pi + 0.5) * H - 0.5], axis=-1)
 
 
-def _roll_rows(rows, roll_dist, clip01, eps=1e-9):
+def _identity_map(n):
+    return np.stack([np.arange(n, dtype=np.int32), np.full(n, -1, np.int32)], 1)
+
+
+def _roll_rows(rows, roll_dist, clip01, eps=1e-9, row_map=False):
     """rows: float64 [n, 5] (label, x1, y1, x2, y2) normalised.  Shifts x by roll_dist, applies the wrap rule and the seam merge of
-    the module docstring (RollAug step 2) and returns the new rows; `rows` is modified."""
+    the module docstring (RollAug step 2) and returns the new rows; `rows` is modified.  row_map=True: also the int32 [n_out, 2]
+    provenance of the returned rows (module docstring, "Row provenance")."""
     x1, x2 = rows[:, 1], rows[:, 3]
     x1 += roll_dist
     x2 += roll_dist
@@ -366,25 +392,31 @@ def _roll_rows(rows, roll_dist, clip01, eps=1e-9):
     left = list(set(np.flatnonzero(np.abs(x1 - roll_dist) < eps).tolist()))
     right = list(set(np.flatnonzero(np.abs(x2 - roll_dist) < eps).tolist()))
     if not left or not right:
-        return rows.copy()
+        return (rows.copy(), _identity_map(len(rows))) if row_map else rows.copy()
     emitted = []
     for i in left:
         for j in right:
             rows[j, 3] = rows[i, 3]
             emitted.append(j)
+    n_merged = len(emitted)
     paired = set(left) | set(right)
     emitted += [i for i in range(len(rows)) if i not in paired]
-    return rows[emitted]
+    if not row_map:
+        return rows[emitted]
+    prov = np.array([[j, left[-1] if k < n_merged else -1] for k, j in enumerate(emitted)], np.int32).reshape(-1, 2)
+    return rows[emitted], prov
 
 
-def transform_one(boxes, labels, H, W, stretch, kx, ky, roll, roll_dist, flip, clip01=True):
-    """One image's boxes (float32 [n, 4] x1 y1 x2 y2 pixels) and labels (int64 [n]) through PanoStretch, RollAug and RandomFlip."""
+def transform_one(boxes, labels, H, W, stretch, kx, ky, roll, roll_dist, flip, clip01=True, row_map=False):
+    """One image's boxes (float32 [n, 4] x1 y1 x2 y2 pixels) and labels (int64 [n]) through PanoStretch, RollAug and RandomFlip.
+    row_map=True: a third result, the int32 [n_out, 2] provenance of the returned rows."""
     boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
     labels = np.asarray(labels, np.int64).reshape(-1)
     if len(boxes) != len(labels):
         raise PswinError(f"transform_boxes: {len(boxes)} boxes but {len(labels)} labels")
+    prov = _identity_map(len(boxes))
     if len(boxes) == 0:
-        return boxes.copy(), labels.copy()
+        return (boxes.copy(), labels.copy(), prov) if row_map else (boxes.copy(), labels.copy())
     if stretch:
         rows = np.concatenate([labels[:, None], boxes], 1)                       # float64, as the reference's concatenate
         pts = _stretch_corners(rows[:, 1:].copy().reshape(-1, 2), H, W, kx, ky).reshape(-1, 4)
@@ -394,7 +426,7 @@ def transform_one(boxes, labels, H, W, stretch, kx, ky, roll, roll_dist, flip, c
         xyxy = boxes.astype(np.float64)
         xyxy[:, [0, 2]] /= W
         xyxy[:, [1, 3]] /= H
-        rows = _roll_rows(np.concatenate([labels[:, None], xyxy], 1), roll_dist, clip01)
+        rows, prov = _roll_rows(np.concatenate([labels[:, None], xyxy], 1), roll_dist, clip01, row_map=True)
         labels = np.round(rows[:, 0]).astype(np.int64)
         xyxy = rows[:, 1:]
         xyxy[:, [0, 2]] *= W
@@ -405,20 +437,22 @@ def transform_one(boxes, labels, H, W, stretch, kx, ky, roll, roll_dist, flip, c
         f[:, 0] = W - boxes[:, 2]
         f[:, 2] = W - boxes[:, 0]
         boxes = f
-    return boxes, labels
+    return (boxes, labels, prov) if row_map else (boxes, labels)
 
 
-def transform_boxes(boxes, labels, H, W, params, clip01=True):
-    """Lists of per-image boxes and labels through PanoStretch, RollAug and RandomFlip with the drawn `params`."""
+def transform_boxes(boxes, labels, H, W, params, clip01=True, row_map=False):
+    """Lists of per-image boxes and labels through PanoStretch, RollAug and RandomFlip with the drawn `params`.  row_map=True: a third
+    list, the row provenance of every image."""
     if len(boxes) != len(params["stretch"]) or len(labels) != len(boxes):
         raise PswinError("transform_boxes: one boxes and one labels array per image of params")
-    out_b, out_l = [], []
+    out_b, out_l, out_m = [], [], []
     for i in range(len(boxes)):
-        b, l = transform_one(boxes[i], labels[i], H, W, params["stretch"][i], params["kx"][i], params["ky"][i], params["roll"][i],
-                             params["roll_dist"][i], params["flip"][i], clip01)
+        b, l, m = transform_one(boxes[i], labels[i], H, W, params["stretch"][i], params["kx"][i], params["ky"][i], params["roll"][i],
+                                params["roll_dist"][i], params["flip"][i], clip01, row_map=True)
         out_b.append(b)
         out_l.append(l)
-    return out_b, out_l
+        out_m.append(m)
+    return (out_b, out_l, out_m) if row_map else (out_b, out_l)
 
 
 def rescale_size(h, w, scale):
@@ -436,9 +470,10 @@ def resize_boxes(boxes, h, w, new_h, new_w):
     return b
 
 
-def crop_boxes(boxes, labels, offset_w, offset_h, crop_h, crop_w):
+def crop_boxes(boxes, labels, offset_w, offset_h, crop_h, crop_w, row_map=None):
     """mmdet RandomCrop._crop_data on the boxes (transforms.py:881-900): subtract the offset in float32, clip to the crop, keep the
-    boxes with x2 > x1 and y2 > y1 and their labels.  crop_h, crop_w: the crop as taken.  An empty result is valid."""
+    boxes with x2 > x1 and y2 > y1 and their labels.  crop_h, crop_w: the crop as taken.  An empty result is valid.  row_map (the
+    int32 [n, 2] provenance of `boxes`, or True for the identity): a third result, the provenance of the rows kept."""
     b = np.asarray(boxes, np.float32).reshape(-1, 4) - np.array([offset_w, offset_h, offset_w, offset_h], dtype=np.float32)
     labels = np.asarray(labels, np.int64).reshape(-1)
     if len(b) != len(labels):
@@ -446,16 +481,214 @@ def crop_boxes(boxes, labels, offset_w, offset_h, crop_h, crop_w):
     b[:, 0::2] = np.clip(b[:, 0::2], 0, crop_w)
     b[:, 1::2] = np.clip(b[:, 1::2], 0, crop_h)
     keep = (b[:, 2] > b[:, 0]) & (b[:, 3] > b[:, 1])
-    return b[keep, :], labels[keep]
+    if row_map is None:
+        return b[keep, :], labels[keep]
+    return b[keep, :], labels[keep], _as_row_map(row_map, len(b), "crop_boxes")[keep]
 
 
-def auto_augment_boxes(boxes, labels, h, w, aa):
-    """One image's boxes and labels through the policy that draw_auto_augment returned for its h x w image."""
+def _as_row_map(row_map, n, what):
+    if row_map is True:
+        return _identity_map(n)
+    m = np.asarray(row_map, np.int32).reshape(-1, 2)
+    if len(m) != n:
+        raise PswinError(f"{what}: the row map has {len(m)} rows for {n} boxes")
+    return m
+
+
+def auto_augment_boxes(boxes, labels, h, w, aa, row_map=None):
+    """One image's boxes and labels through the policy that draw_auto_augment returned for its h x w image.  row_map (the provenance
+    of `boxes`, e.g. transform_one's, or True for the identity): a third result, the composed provenance of the returned rows -- what
+    pswin_pano_masks takes."""
     h1, w1, cy, cx, ch, cw, oh, ow = aa["plan"]
     if aa["policy"] == 0:
-        return resize_boxes(boxes, h, w, oh, ow), np.asarray(labels, np.int64).reshape(-1)
-    b, l = crop_boxes(resize_boxes(boxes, h, w, h1, w1), labels, cx, cy, ch, cw)
-    return resize_boxes(b, ch, cw, oh, ow), l
+        b, l = resize_boxes(boxes, h, w, oh, ow), np.asarray(labels, np.int64).reshape(-1)
+        return (b, l) if row_map is None else (b, l, _as_row_map(row_map, len(b), "auto_augment_boxes").copy())
+    if row_map is None:
+        b, l = crop_boxes(resize_boxes(boxes, h, w, h1, w1), labels, cx, cy, ch, cw)
+        return resize_boxes(b, ch, cw, oh, ow), l
+    b, l, m = crop_boxes(resize_boxes(boxes, h, w, h1, w1), labels, cx, cy, ch, cw, row_map)
+    return resize_boxes(b, ch, cw, oh, ow), l, m
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# instance masks: the definition (host, numpy) and the launch
+# ------------------------------------------------------------------------------------------------------------------------------
+
+def nn_index(d, n_in, n_out):
+    """Source index of output index d (int or array) of a nearest-neighbour resize n_in -> n_out: cv2.resize(INTER_NEAREST)'s rule,
+    min(int(floor(d * (1 / (n_out / n_in)))), n_in - 1) in float64.  PARITY: unpinned (module docstring, "Instance masks")."""
+    inv = 1.0 / (np.float64(n_out) / np.float64(n_in))
+    return np.minimum(np.floor(np.asarray(d, np.float64) * inv).astype(np.int64), n_in - 1)
+
+
+def _wrap_taps(c, n):
+    """scipy's order-1 taps on axis n with the 'wrap' boundary of period n - 1 (module docstring): i0, i1, w0, w1."""
+    sz = n - 1
+    c = np.array(c, np.float64)
+    neg, big = c < 0, c > n - 1
+    c[neg] += sz * ((-c[neg] / sz).astype(np.int64) + 1)
+    c[big] -= sz * (c[big] / sz).astype(np.int64)
+    f = np.floor(c)
+    w0 = 1.0 - (c - f)
+    i0 = f.astype(np.int64)
+    return i0, np.minimum(i0 + 1, n - 1), w0, 1.0 - w0
+
+
+def sample_plane01(p, refy, refx):
+    """A float64 0 / 1 plane sampled at (refy, refx) (arrays that broadcast) as the stretch samples the image: wrap taps, the blend
+    accumulated row-major as (value * wy) * wx, rounded half-up -- 1 where the blend reaches 0.5, else 0."""
+    H, W = p.shape
+    ya, yb, wy0, wy1 = _wrap_taps(refy, H)
+    xa, xb, wx0, wx1 = _wrap_taps(refx, W)
+    t = 0.0 + p[ya, xa] * wy0 * wx0
+    t = t + p[ya, xb] * wy0 * wx1
+    t = t + p[yb, xa] * wy1 * wx0
+    t = t + p[yb, xb] * wy1 * wx1
+    return np.floor(t + 0.5)
+
+
+def warp_plane01(plane, stretch, kx, ky, shift, flip):
+    """Wm of one bitmap: the 0 / 1 plane `plane != 0` ([H, W]) through the image's warp as a one-channel image -- the stretch with the
+    module docstring's coordinates, taps and half-up rounding, then the roll by `shift` columns, then the flip.  uint8 0 / 1."""
+    p = (np.asarray(plane) != 0).astype(np.float64)
+    H, W = p.shape
+    if stretch:
+        u = ((np.arange(W, dtype=np.float64) + 0.5) / W - 0.5) * 2 * np.pi
+        v = ((np.arange(H, dtype=np.float64) + 0.5) / H - 0.5) * np.pi
+        su = np.sin(u)
+        u0 = np.arctan2(su * kx / ky, np.cos(u))
+        v0 = np.arctan(np.tan(v)[:, None] * np.sin(u0)[None, :] / su[None, :] * ky)
+        p = sample_plane01(p, (v0 / np.pi + 0.5) * H - 0.5, ((u0 / (2 * np.pi) + 0.5) * W - 0.5)[None, :])
+    p = np.roll(p, int(shift), axis=1)
+    if flip:
+        p = p[:, ::-1]
+    return np.ascontiguousarray(p).astype(np.uint8)
+
+
+def mask_source_index(H, W, plan):
+    """(sy int64 [oh], sx int64 [ow]) of a plan: the row and the column of the warped H x W plane that output pixel (y, x) shows."""
+    h1, w1, cy, cx, ch, cw, oh, ow = (int(v) for v in plan)
+    ys, xs = np.arange(oh), np.arange(ow)
+    if h1 == 0:
+        return nn_index(ys, H, oh), nn_index(xs, W, ow)
+    return nn_index(cy + nn_index(ys, ch, oh), H, h1), nn_index(cx + nn_index(xs, cw, ow), W, w1)
+
+
+def transform_masks_one(src, stretch, kx, ky, shift, flip, plan, rows, pad_hw):
+    """The definition of pswin_pano_masks for one image.  src: uint8 [n_in, H, W] bitmaps (a byte is set when it is not zero); plan:
+    (h1, w1, cy, cx, ch, cw, oh, ow) as resize_crop_resize_normalize_pad defines it; rows: int32 [n_out, 2] row provenance (entries
+    outside [0, n_in) read nothing); pad_hw = (Hp, Wp).  Returns uint8 [n_out, Hp, Wp] of 0 / 1:
+
+        out[r, y, x] = max over the sources a of rows[r] of Wm[a][sy[y], sx[x]]     inside oh x ow, 0 in the pad,
+
+    Wm = warp_plane01, (sy, sx) = mask_source_index.  Resize, crop and resize are nearest-neighbour index chains (nn_index), as
+    BitmapMasks.rescale / crop / resize; the stretch and the roll have no mask path in the reference: the mask goes where the image
+    goes, by the image's own expression, which on a 0 / 1 plane gives 0 / 1 again."""
+    src = np.asarray(src)
+    n_in, H, W = src.shape
+    Hp, Wp = int(pad_hw[0]), int(pad_hw[1])
+    oh, ow = int(plan[6]), int(plan[7])
+    rows = np.asarray(rows, np.int64).reshape(-1, 2)
+    out = np.zeros((len(rows), Hp, Wp), np.uint8)
+    sy, sx = mask_source_index(H, W, plan)
+    warped = {}
+    for r, pair in enumerate(rows):
+        for a in pair:
+            if 0 <= a < n_in:
+                if a not in warped:
+                    warped[a] = warp_plane01(src[a], stretch, kx, ky, shift, flip)
+                out[r, :oh, :ow] = np.maximum(out[r, :oh, :ow], warped[a][sy][:, sx])
+    return out
+
+
+def transform_masks(masks, params, plans, rows, pad_hw):
+    """transform_masks_one over a batch: masks a list of [n_i, H, W], params the drawn dict, plans and rows one entry per image."""
+    return [transform_masks_one(masks[i], params["stretch"][i], params["kx"][i], params["ky"][i], params["shift"][i], params["flip"][i],
+                                plans[i], rows[i], pad_hw) for i in range(len(masks))]
+
+
+def masks_addressable(B, Gin, Gmax, H, W, Hp, Wp):
+    """What pswin_pano_masks can index: offsets inside a source or an output plane are 32-bit, the bases of the planes 64-bit, the grid
+    has B layers and ceil(Hp / 16) rows of workgroups."""
+    return H * W < 2 ** 31 and Hp * Wp < 2 ** 31 and B * Gmax < 2 ** 31 and B * Gin < 2 ** 31 and B <= 65535 and -(-Hp // 16) <= 65535
+
+
+def pack_rows(rows, max_gt):
+    """Host lists of per-image row maps -> (int32 [B, max_gt, 2] padded with -1, int32 [B] counts)."""
+    maps = [np.asarray(r, np.int32).reshape(-1, 2) for r in rows]
+    if max(len(m) for m in maps) > max_gt:
+        raise PswinError(f"pack_rows: an image has {max(len(m) for m in maps)} rows, max_gt = {max_gt}")
+    packed = np.full((len(maps), max_gt, 2), -1, np.int32)
+    for b, m in enumerate(maps):
+        packed[b, :len(m)] = m
+    return packed, np.array([len(m) for m in maps], np.int32)
+
+
+def warp_resize_masks(src, params, plan, rows, count=None, pad_hw=None, size_divisor=32, out=None):
+    """pswin_pano_masks: the bitmaps of a batch through stretch, roll, flip, resize (-> crop -> resize) and pad in one launch, every
+    byte of the result written.  src: device uint8 [B, Gin, H, W]; params: the drawn dict or a device float64 [B, 4] tensor; plan: host
+    rows as resize_crop_resize_normalize_pad takes them (validated here) or a device int32 [B, 8] tensor (clamped on the device; then
+    pad_hw must be given); rows: a host list of per-image [n_i, 2] maps (count is then theirs, and Gmax that of `out`, else the largest
+    n_i, at least 1) or a device int32 [B, Gmax, 2] tensor with count a device int32 [B] tensor.  Returns uint8 [B, Gmax, Hp, Wp]."""
+    what = "warp_resize_masks"
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise PswinError(f"{what}: the PanoSwin kernels run on an MI355X (HIP) device only; got a CPU tensor")
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[1] < 1:
+        raise PswinError(f"{what}: expected uint8 [B, Gin, H, W] bitmaps with Gin >= 1, got {src.dtype} {tuple(src.shape)}")
+    B, Gin, H, W = src.shape
+    dev = src.device
+    if W % 2:
+        raise PswinError(f"{what}: the width must be even (sin u = 0 at x = (W-1)/2), got {W}")
+    if H < 2:
+        raise PswinError(f"{what}: the height must be at least 2, got {H}")
+    if isinstance(params, dict):
+        params = params_tensor(params, dev)
+    if not isinstance(params, torch.Tensor) or params.dtype != torch.float64 or tuple(params.shape) != (B, 4) or params.device != dev \
+            or not params.is_contiguous():
+        raise PswinError(f"{what}: params must be a contiguous float64 [B, 4] tensor on the bitmaps' device")
+    if isinstance(plan, torch.Tensor):
+        if pad_hw is None:
+            raise PswinError(f"{what}: pass pad_hw with a device plan tensor")
+        if plan.dtype != torch.int32 or tuple(plan.shape) != (B, 8) or plan.device != dev or not plan.is_contiguous():
+            raise PswinError(f"{what}: plan must be a contiguous int32 [B, 8] tensor on the bitmaps' device")
+        plan_t = plan
+    else:
+        host = _host_plan(plan, B, what)
+        sizes = [(r[6], r[7]) for r in host]
+        if pad_hw is None:
+            pad_hw = padded_size(sizes, size_divisor)
+        if any(h > pad_hw[0] or w > pad_hw[1] for h, w in sizes):
+            raise PswinError(f"{what}: an output size exceeds the padded size {tuple(pad_hw)}")
+        plan_t = torch.tensor(host, dtype=torch.int32, device=dev)
+    Hp, Wp = int(pad_hw[0]), int(pad_hw[1])
+    if Hp < 1 or Wp < 1:
+        raise PswinError(f"{what}: the padded size must be positive, got {pad_hw}")
+    if isinstance(rows, torch.Tensor):
+        if rows.dtype != torch.int32 or rows.dim() != 3 or rows.shape[0] != B or rows.shape[1] < 1 or rows.shape[2] != 2 \
+                or rows.device != dev or not rows.is_contiguous():
+            raise PswinError(f"{what}: rows must be a contiguous int32 [B, Gmax, 2] tensor on the bitmaps' device")
+        if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or tuple(count.shape) != (B,) or count.device != dev \
+                or not count.is_contiguous():
+            raise PswinError(f"{what}: with a device rows tensor, count must be a contiguous int32 [B] tensor on the same device")
+        rows_t, count_t = rows, count
+    else:
+        if count is not None or len(rows) != B:
+            raise PswinError(f"{what}: host rows are one [n_i, 2] map per image ({B}), and carry their own count")
+        max_gt = out.shape[1] if isinstance(out, torch.Tensor) and out.dim() == 4 else max(1, max(len(r) for r in rows))
+        packed, counts = pack_rows(rows, max_gt)
+        rows_t, count_t = torch.from_numpy(packed).to(dev), torch.from_numpy(counts).to(dev)
+    Gmax = rows_t.shape[1]
+    if not masks_addressable(B, Gin, Gmax, H, W, Hp, Wp):
+        raise PswinError(f"{what}: B = {B}, Gin = {Gin}, Gmax = {Gmax}, {H} x {W} -> {Hp} x {Wp} is past what the kernel can index "
+                         "(masks_addressable)")
+    x = src.contiguous()
+    if out is None:
+        out = torch.empty(B, Gmax, Hp, Wp, device=dev, dtype=torch.uint8)
+    else:
+        _check_buffer(out, what, "out", torch.uint8, (B, Gmax, Hp, Wp), dev, (x, params, plan_t, rows_t, count_t))
+    _lib.call("pswin_pano_masks", x, _lib.ptr(x), _lib.ptr(params), _lib.ptr(plan_t), _lib.ptr(rows_t), _lib.ptr(count_t), _lib.ptr(out),
+              B, Gin, Gmax, H, W, Hp, Wp, algo_bytes=x.numel() + out.numel())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -501,28 +734,6 @@ class PanoTrainTransform:
             aas.append(draw_auto_augment(H, W, self.auto_augment, self.rng, self.img_scales))
         return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}, aas
 
-    def _call_auto(self, imgs_u8, boxes, labels):
-        B, H, W, _ = imgs_u8.shape
-        params, aas = self.draw_auto(B, H, W)
-        plan = [a["plan"] for a in aas]
-        pad_hw = padded_size([p[6:] for p in plan], self.size_divisor)
-        dev = imgs_u8.device
-        if dev not in self._norm:
-            self._norm[dev] = norm_tensor(self.mean, self.std, dev)
-        x = resize_crop_resize_normalize_pad(pano_warp(imgs_u8, params), plan, to_rgb=self.to_rgb, size_divisor=self.size_divisor,
-                                             pad_hw=pad_hw, norm=self._norm[dev])
-        boxes, labels = transform_boxes(boxes, labels, H, W, params, self.clip01)
-        metas = []
-        d = self.size_divisor or 1
-        for i, a in enumerate(aas):
-            h1, w1, cy, cx, ch, cw, nh, nw = a["plan"]
-            boxes[i], labels[i] = auto_augment_boxes(boxes[i], labels[i], H, W, a)
-            fh, fw = (ch, cw) if a["policy"] else (H, W)                   # what the final resize took in
-            m = self._meta(params, i, H, W, nh, nw, fh, fw, a["scale"], pad_hw, d)
-            m.update(auto_augment_policy=a["policy"], crop=a["crop"], pano_ratio_v=a["pano_ratio_v"], pano_lr_noadj=a["pano_lr_noadj"])
-            metas.append(m)
-        return x, boxes, labels, metas
-
     def _meta(self, params, i, H, W, nh, nw, fh, fw, scale, pad_hw, d):
         return dict(ori_shape=(H, W, 3), img_shape=(nh, nw, 3), pad_shape=(-(-nh // d) * d, -(-nw // d) * d, 3),
                     batch_input_shape=tuple(pad_hw), scale=scale,
@@ -533,24 +744,118 @@ class PanoTrainTransform:
                     img_norm_cfg=dict(mean=np.array(self.mean, np.float32), std=np.array(self.std, np.float32),
                                       to_rgb=self.to_rgb))
 
-    def __call__(self, imgs_u8, boxes, labels):
+    def _run(self, imgs_u8, boxes, labels):
+        """The draws, the two launches and the host side of both recipes: (x, boxes, labels, metas) and what the mask launch needs
+        (params, plan rows, pad_hw, the composed row maps)."""
         _check_images(imgs_u8, "PanoTrainTransform", (3,))
         B, H, W, _ = imgs_u8.shape
         if len(boxes) != B or len(labels) != B:
             raise PswinError(f"PanoTrainTransform: {B} images but {len(boxes)} box arrays and {len(labels)} label arrays")
-        if self.auto_augment is not None:
-            return self._call_auto(imgs_u8, boxes, labels)
-        params, scales = self.draw(B, W)
-        sizes = [rescale_size(H, W, s) for s in scales]
-        pad_hw = padded_size(sizes, self.size_divisor)
         dev = imgs_u8.device
+        d = self.size_divisor or 1
+        if self.auto_augment is not None:
+            params, aas = self.draw_auto(B, H, W)
+            plan = [a["plan"] for a in aas]
+        else:
+            params, scales = self.draw(B, W)
+            plan = [(0, 0, 0, 0, 0, 0) + rescale_size(H, W, s) for s in scales]
+        pad_hw = padded_size([p[6:] for p in plan], self.size_divisor)
         if dev not in self._norm:
             self._norm[dev] = norm_tensor(self.mean, self.std, dev)
         warped = pano_warp(imgs_u8, params)
-        x = resize_normalize_pad(warped, sizes, to_rgb=self.to_rgb, size_divisor=self.size_divisor, pad_hw=pad_hw, norm=self._norm[dev])
-        boxes, labels = transform_boxes(boxes, labels, H, W, params, self.clip01)
+        if self.auto_augment is not None:
+            x = resize_crop_resize_normalize_pad(warped, plan, to_rgb=self.to_rgb, size_divisor=self.size_divisor, pad_hw=pad_hw,
+                                                 norm=self._norm[dev])
+        else:
+            x = resize_normalize_pad(warped, [p[6:] for p in plan], to_rgb=self.to_rgb, size_divisor=self.size_divisor, pad_hw=pad_hw,
+                                     norm=self._norm[dev])
+        boxes, labels, maps = transform_boxes(boxes, labels, H, W, params, self.clip01, row_map=True)
         metas = []
-        for i, (nh, nw) in enumerate(sizes):
-            boxes[i] = resize_boxes(boxes[i], H, W, nh, nw)
-            metas.append(self._meta(params, i, H, W, nh, nw, H, W, scales[i], pad_hw, self.size_divisor or 1))
-        return x, boxes, labels, metas
+        for i in range(B):
+            h1, w1, cy, cx, ch, cw, nh, nw = plan[i]
+            if self.auto_augment is not None:
+                a = aas[i]
+                boxes[i], labels[i], maps[i] = auto_augment_boxes(boxes[i], labels[i], H, W, a, maps[i])
+                fh, fw = (ch, cw) if a["policy"] else (H, W)               # what the final resize took in
+                m = self._meta(params, i, H, W, nh, nw, fh, fw, a["scale"], pad_hw, d)
+                m.update(auto_augment_policy=a["policy"], crop=a["crop"], pano_ratio_v=a["pano_ratio_v"], pano_lr_noadj=a["pano_lr_noadj"])
+            else:
+                boxes[i] = resize_boxes(boxes[i], H, W, nh, nw)
+                m = self._meta(params, i, H, W, nh, nw, H, W, scales[i], pad_hw, d)
+            metas.append(m)
+        return (x, boxes, labels, metas), (params, plan, pad_hw, maps)
+
+    def __call__(self, imgs_u8, boxes, labels):
+        return self._run(imgs_u8, boxes, labels)[0]
+
+    def with_targets(self, imgs_u8, boxes, labels, masks=None, out=None):
+        """__call__ with the annotations as the detector takes them:
+
+            x, targets, img_metas = PanoTrainTransform(...).with_targets(imgs_u8, boxes, labels, masks=None, out=None)
+
+        The draws, x, the boxes, the labels and img_metas are those of __call__ under the same RNG state.  targets is a
+        detector.PaddedTargets: boxes, labels and count filled by one copy each, masks (uint8 [B, Gmax, Hp, Wp], the padded input's
+        resolution) by one launch of pswin_pano_masks (warp_resize_masks), every byte.  masks: a list of per-image [n_i, H, W] uint8
+        arrays or tensors, one bitmap per input box, or one packed device tensor [B, Gin, H, W] (rows past an image's boxes are
+        ignored); None gives targets.masks = None, the Faster R-CNN form.  out: a PaddedTargets to write in place (its max_gt must
+        hold the batch's rows and its masks have this batch's padded size); None allocates one with Gmax = the largest count, at
+        least 1."""
+        from .detector import PaddedTargets
+        what = "PanoTrainTransform.with_targets"
+        n_in = [int(np.asarray(b).reshape(-1, 4).shape[0]) for b in boxes]
+        (x, boxes, labels, metas), (params, plan, pad_hw, maps) = self._run(imgs_u8, boxes, labels)
+        B, H, W, _ = imgs_u8.shape
+        dev = imgs_u8.device
+        counts = [len(b) for b in boxes]
+        if out is None:
+            Gmax = max(1, max(counts))
+            out = PaddedTargets(torch.empty(B, Gmax, 4, device=dev), torch.empty(B, Gmax, dtype=torch.long, device=dev),
+                                torch.empty(B, dtype=torch.int32, device=dev),
+                                None if masks is None else torch.empty(B, Gmax, pad_hw[0], pad_hw[1], dtype=torch.uint8, device=dev))
+        else:
+            if not isinstance(out, PaddedTargets):
+                raise PswinError(f"{what}: out must be a PaddedTargets, got {type(out).__name__}")
+            Gmax = out.boxes.shape[1] if out.boxes.dim() == 3 else -1
+            if tuple(out.boxes.shape) != (B, Gmax, 4) or tuple(out.labels.shape) != (B, Gmax) or tuple(out.count.shape) != (B,):
+                raise PswinError(f"{what}: out holds boxes {tuple(out.boxes.shape)}, labels {tuple(out.labels.shape)}, count "
+                                 f"{tuple(out.count.shape)}; the batch has {B} images")
+            if max(counts) > Gmax:
+                raise PswinError(f"{what}: an image has {max(counts)} boxes, out holds max_gt = {Gmax}")
+            if (masks is None) != (out.masks is None):
+                raise PswinError(f"{what}: masks must be given exactly when out has a mask buffer")
+            if masks is not None and tuple(out.masks.shape) != (B, Gmax) + tuple(pad_hw):
+                raise PswinError(f"{what}: out.masks is {tuple(out.masks.shape)}, this batch needs {(B, Gmax) + tuple(pad_hw)}")
+        if masks is not None:
+            src = self._pack_masks(masks, n_in, B, H, W, dev, what)
+            packed, _ = pack_rows(maps, Gmax)
+        hb, hl = np.zeros((B, Gmax, 4), np.float32), np.zeros((B, Gmax), np.int64)
+        for b, n in enumerate(counts):
+            hb[b, :n], hl[b, :n] = boxes[b], labels[b]
+        out.boxes.copy_(torch.from_numpy(hb))
+        out.labels.copy_(torch.from_numpy(hl))
+        out.count.copy_(torch.tensor(counts, dtype=torch.int32))
+        out.list_counts = None
+        if masks is not None:
+            warp_resize_masks(src, params, plan, torch.from_numpy(packed).to(dev), out.count, pad_hw=pad_hw, out=out.masks)
+        return x, out, metas
+
+    @staticmethod
+    def _pack_masks(masks, n_in, B, H, W, dev, what):
+        """The source bitmaps as one device uint8 [B, Gin, H, W] tensor: a packed tensor as it is, a list padded with zero planes."""
+        if isinstance(masks, torch.Tensor):
+            if not masks.is_cuda or masks.device != dev or masks.dtype != torch.uint8 or masks.dim() != 4 or masks.shape[0] != B \
+                    or tuple(masks.shape[2:]) != (H, W) or masks.shape[1] < max(1, max(n_in)):
+                raise PswinError(f"{what}: packed masks must be a uint8 [B, Gin, {H}, {W}] tensor on {dev} with Gin >= every image's "
+                                 f"boxes ({max(n_in)}); got {masks.dtype} {tuple(masks.shape)} on {masks.device}")
+            return masks
+        if len(masks) != B:
+            raise PswinError(f"{what}: {B} images but {len(masks)} mask arrays")
+        src = torch.zeros(B, max(1, max(n_in)), H, W, dtype=torch.uint8, device=dev)
+        for b, m in enumerate(masks):
+            m = torch.as_tensor(m)
+            if m.dtype != torch.uint8 or tuple(m.shape) != (n_in[b], H, W):
+                raise PswinError(f"{what}: image {b} needs uint8 masks of shape {(n_in[b], H, W)}, one per box; got {m.dtype} "
+                                 f"{tuple(m.shape)}")
+            if n_in[b]:
+                src[b, :n_in[b]].copy_(m)
+        return src
