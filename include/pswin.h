@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSWIN_ABI_VERSION 8
+#define PSWIN_ABI_VERSION 9
 
 #define PSWIN_F32 0
 #define PSWIN_BF16 1
@@ -368,8 +368,16 @@ typedef struct pswin_tn_job {
     float* dbias_partial; /* f32 [splits, N] or NULL */
     long long M;
     int N, K, splits, partial_dtype, zero_lo, zero_hi;
+    /* Sample liveness (optional; NULL = every row is contracted): the rows are sample-major, sample b owns rows [b * rows_per_sample,
+     * (b + 1) * rows_per_sample), M = B * rows_per_sample with B <= 64, and sample_scale is the f32 [B] per-sample DropPath factor
+     * vector on the device.  sample_scale[b] == 0 declares sample b dead: its rows of dy are exact zeros, and the 64-row slabs that
+     * lie entirely inside dead samples are not read (neither operand); slabs that straddle a live sample are contracted as always. */
+    const float* sample_scale;
+    int rows_per_sample;
 } pswin_tn_job;
 int pswin_gemm_tn_ring_jobs(const pswin_tn_job* jobs, int n_jobs, void* stream);
+/* bytes of the job table one launch carries in its kernel arguments (<= 4,000: the 4 KB segment) */
+int pswin_gemm_tn_ring_table_bytes(void);
 
 typedef struct pswin_transpose_job {
     const void* src; /* bf16 [rows][cols] */
@@ -538,6 +546,19 @@ int pswin_gemm_nt_gelu_fwd(const void* x, const void* w, const float* bias, void
 int pswin_gemm_nt_partial_rows(long long M, int tile_m);
 int pswin_gemm_nt_gelu_bwd(const void* dy, const void* w_t, const void* pre, const float* bias, void* dpre, float* partial, long long M,
                            int K, int N, int tile_m, void* stream);
+/* The three products above with SAMPLE LIVENESS (the Mlp under per-sample DropPath): rows are sample-major, sample b owns rows
+ * [b * rows_per_sample, (b + 1) * rows_per_sample), M = B * rows_per_sample, B <= 64, rows_per_sample a multiple of the row tile;
+ * sample_scale: the f32 [B] DropPath factor vector on the device, sample b is DEAD iff sample_scale[b] == 0.  The tiles of the live
+ * samples are compacted into the first workgroups of the (unchanged) grid and computed as always; a dead sample's rows are neither read
+ * nor multiplied: pswin_gemm_nt_live writes zeros to its rows of y, pswin_gemm_nt_gelu_bwd_live writes zero rows of `partial` and
+ * leaves its rows of dpre UNWRITTEN, pswin_gemm_nt_gelu_fwd_live leaves its rows of pre and h UNWRITTEN -- whoever reads those must
+ * skip the same rows.  sample_scale = NULL: the entry point without the suffix. */
+int pswin_gemm_nt_live(const void* x, const void* w, const float* bias, void* y, long long M, int K, int N, int tile_m,
+                       const float* sample_scale, int rows_per_sample, void* stream);
+int pswin_gemm_nt_gelu_fwd_live(const void* x, const void* w, const float* bias, void* pre, void* h, long long M, int K, int N, int tile_m,
+                                const float* sample_scale, int rows_per_sample, void* stream);
+int pswin_gemm_nt_gelu_bwd_live(const void* dy, const void* w_t, const void* pre, const float* bias, void* dpre, float* partial, long long M,
+                                int K, int N, int tile_m, const float* sample_scale, int rows_per_sample, void* stream);
 
 /* Streaming GEMM for the Linear layers of the high-resolution stages (qkv / proj / fc1 / fc2 of stage 0, HOT:287, 309,
  * 50-58; proj of stage 1):  y[M, N] = x[M, K] . W^T (+ bias), bf16 in / out, f32 accumulation, the whole weight resident

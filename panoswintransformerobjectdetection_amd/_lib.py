@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PSWIN_LIB") or os.path.join(_PKG, "libpswin_hip.so") 
 F32, BF16 = 0, 1
 MODE_PLANAR, MODE_PANO = 0, 1
 WS, WTOK, WPAD, HEAD_DIM = 7, 49, 64, 32
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -67,6 +67,7 @@ _PROTOTYPES = {
     "pswin_gemm_tn_ring": [_vp, _vp, _vp, _i, ctypes.c_longlong, _i, _i, _i, _vp],
     "pswin_gemm_tn_ring_bias": [_vp, _vp, _vp, _i, _vp, _i, _i, ctypes.c_longlong, _i, _i, _i, _vp],
     "pswin_gemm_tn_ring_jobs": [_vp, _i, _vp],
+    "pswin_gemm_tn_ring_table_bytes": [],
     "pswin_transpose_jobs": [_vp, _i, _vp],
     "pswin_adamw_flat": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp],
     "pswin_adamw_flat_groups": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _i, _vp, _vp, ctypes.c_double, ctypes.c_double,
@@ -128,6 +129,9 @@ _PROTOTYPES = {
     "pswin_gemm_nt_gelu_fwd": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],
     "pswin_gemm_nt_partial_rows": [ctypes.c_longlong, _i],
     "pswin_gemm_nt_gelu_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],
+    "pswin_gemm_nt_live": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp, _i, _vp],
+    "pswin_gemm_nt_gelu_fwd_live": [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp, _i, _vp],
+    "pswin_gemm_nt_gelu_bwd_live": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp, _i, _vp],
     "pswin_gemm_skinny_supported": [_i, _i],
     "pswin_gemm_skinny": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp],
     "pswin_fc1_gelu_supported": [_i, _i],
@@ -191,7 +195,7 @@ class TnJob(ctypes.Structure):
     """pswin_tn_job of include/pswin.h"""
     _fields_ = [("dy", ctypes.c_void_p), ("x", ctypes.c_void_p), ("partial", ctypes.c_void_p), ("dbias_partial", ctypes.c_void_p),
                 ("M", ctypes.c_longlong), ("N", ctypes.c_int), ("K", ctypes.c_int), ("splits", ctypes.c_int), ("partial_dtype", ctypes.c_int),
-                ("zero_lo", ctypes.c_int), ("zero_hi", ctypes.c_int)]
+                ("zero_lo", ctypes.c_int), ("zero_hi", ctypes.c_int), ("sample_scale", ctypes.c_void_p), ("rows_per_sample", ctypes.c_int)]
 
 
 class TransposeJob(ctypes.Structure):

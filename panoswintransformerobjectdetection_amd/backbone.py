@@ -79,8 +79,9 @@ class Mlp(nn.Module):
     def forward(self, x, cd):
         return _linear(F.gelu(_linear(x, self.fc1, cd)), self.fc2, cd)
 
-    def forward_nobias2(self, x, cd):
-        """fc2(gelu(fc1 x + b1)) WITHOUT fc2's bias (the caller adds it with the residual): bias + GELU in one HIP pass"""
+    def forward_nobias2(self, x, cd, sample_scale=None, rows_per_sample=0):
+        """fc2(gelu(fc1 x + b1)) WITHOUT fc2's bias (the caller adds it with the residual): bias + GELU in one HIP pass.
+        sample_scale / rows_per_sample: the branch's per-sample DropPath factors (stages 1-3 leave dropped samples out: ops._MlpFused)"""
         x2 = x.to(cd).reshape(-1, x.shape[-1])
         if self.fc1.bias is not None and ops.mlp0_fused_supported(x2, self.fc1.weight.shape[0]):
             # stage 0: one autograd node; its backward runs fc2's data gradient and the GELU backward in one pass
@@ -91,7 +92,7 @@ class Mlp(nn.Module):
             h = h.view(*x.shape[:-1], h.shape[-1])
         elif self.fc1.bias is not None and ops.mlp_fused_supported(x2, self.fc1.weight.shape[0]):
             # stages 1-3: fc1 (+ bias + GELU in its epilogue) and fc2 as one autograd node on the tiled HIP GEMM
-            return ops.mlp_fused(x2, self.fc1, self.fc2).view(*x.shape[:-1], self.fc2.weight.shape[0])
+            return ops.mlp_fused(x2, self.fc1, self.fc2, sample_scale, rows_per_sample).view(*x.shape[:-1], self.fc2.weight.shape[0])
         else:
             y = _linear(x, self.fc1, cd, use_bias=False)
             if cd == torch.bfloat16 and ops.FUSED_GELU_BWD:
@@ -178,19 +179,22 @@ class PanoSwinTransformerBlock(nn.Module, DoubleModeModule):
             # the second result is x itself: using it for the shortcut folds the shortcut's gradient into the LN backward kernel
             win, x = ops.layer_norm_gather(x, n1.weight, n1.bias, n1.eps, wmap, inv, cd, passthrough=True,
                                            res_bias=a.proj.bias if fuse else None, res_scale=s1)   # [B, nW*49, C]
+        # the window rows of the samples whose attention branch is dropped (s1 == 0) carry exact-zero gradients: the weight gradients of
+        # qkv and proj leave them out
+        live1 = ops.sample_liveness(s1, nW * WTOK, B * nW * WTOK) if fuse else None
         # the K third of d(qkv) sums to zero over every window (rows of dS sum to 0): its bias gradient is not summed
         if fuse and ops.FUSED_WINDOW_ATTENTION and ops.window_attention_fused_supported(win.view(-1, C), a.num_heads):
             # C = 96: qkv Linear, attention and proj Linear of a window in one kernel, weights resident in LDS
             att = ops.window_attention_fused(win.view(-1, C), a, dist, mask, nW).view(B, nW * WTOK, C)
         elif fuse and ops.window_attention_qkv_fused_supported(win.view(-1, C), a.num_heads):
             # C = 192 / 384: qkv Linear + attention core of a (window, head) in one kernel (the head's weight rows resident in LDS)
-            att = ops.window_attention_qkv_fused(win.view(-1, C), a, dist, mask, nW)
-            att = _linear(att, a.proj, cd, use_bias=False).view(B, nW * WTOK, C)
+            att = ops.window_attention_qkv_fused(win.view(-1, C), a, dist, mask, nW, live1)
+            att = _linear(att, a.proj, cd, use_bias=False, live=live1).view(B, nW * WTOK, C)
         else:
-            qkv = _linear(win.view(-1, C), a.qkv, cd, zero_bias_cols=(C, 2 * C))      # [B*nW*49, 3C]
+            qkv = _linear(win.view(-1, C), a.qkv, cd, zero_bias_cols=(C, 2 * C), live=live1)      # [B*nW*49, 3C]
             att = ops.window_attention(qkv, a.sphere_position_alpha_table_Te, a.sphere_position_beta_table_Te, dist, mask,
                                        a.num_heads, a.scale, nW)
-            att = _linear(att, a.proj, cd, use_bias=not fuse).view(B, nW * WTOK, C)
+            att = _linear(att, a.proj, cd, use_bias=not fuse, live=live1).view(B, nW * WTOK, C)
         n2 = self.norm2
         if x.dtype == torch.float32 and C <= 1024:
             # shortcut + DropPath(attn) and norm2 of the sum in one kernel (the sum is not read back by a LayerNorm pass); its backward
@@ -202,7 +206,7 @@ class PanoSwinTransformerBlock(nn.Module, DoubleModeModule):
             x = ops.window_scatter_add(att, x, wmap, inv, s1, a.proj.bias if fuse else None, True)
             h, x = ops.layer_norm_gather(x, n2.weight, n2.bias, n2.eps, out_dtype=cd, passthrough=True,
                                          res_bias=self.mlp.fc2.bias if fuse else None, res_scale=s2)
-        y = self.mlp.forward_nobias2(h, cd) if fuse else self.mlp(h, cd)
+        y = self.mlp.forward_nobias2(h, cd, s2, S) if fuse else self.mlp(h, cd)
         ident = ops.identity_map(S, dev)
         if nxt is not None:
             # x + DropPath(mlp) AND the next block's norm1 + shift + pad + partition in one kernel: (its windows, the new residual stream)

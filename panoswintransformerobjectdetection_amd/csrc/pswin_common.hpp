@@ -165,6 +165,27 @@ __device__ inline void exchange_row8(f32x4& q0, f32x4& q1) {
     q1 = __builtin_bit_cast(f32x4, u32x4{r0[1], r1[1], r2[1], r3[1]});
 }
 
+// Sample liveness (per-sample DropPath): a block branch's factor vector `sample_scale` (f32 [B], B <= 64) with rows_per_sample rows per
+// sample, sample-major.  Sample b is DEAD iff sample_scale[b] == 0.0f: its branch output is multiplied by zero and every gradient
+// that flows into the branch for it is an exact zero, so kernels may leave its rows out.  Everything below is wave-uniform (one lane
+// per sample, one ballot): bit b of the mask = sample b is live.
+constexpr int LIVE_SAMPLES_MAX = 64;
+__device__ inline unsigned long long live_sample_mask(const float* __restrict__ sample_scale, int B) {
+    const int lane = threadIdx.x & 63;
+    const float s = lane < B ? sample_scale[lane] : 0.f;
+    return __ballot(s != 0.0f);
+}
+__device__ inline unsigned long long dead_sample_mask(unsigned long long live, int B) {
+    return ~live & (B >= 64 ? ~0ull : (1ull << B) - 1ull);
+}
+__device__ inline int sample_count(unsigned long long mask) { return __builtin_popcountll(mask); }
+// the k-th (from 0) sample of `mask` in ascending order; k < sample_count(mask)
+__device__ inline int kth_sample(unsigned long long mask, int k) {
+    const int lane = threadIdx.x & 63;
+    const bool hit = ((mask >> lane) & 1ull) && __builtin_popcountll(mask & ((1ull << lane) - 1ull)) == k;
+    return __builtin_ctzll(__ballot(hit));
+}
+
 // out[c] = sum_r part[r][c] (r in fixed order: bitwise reproducible).  16 columns x 64 row lanes per block, so that
 // even 512 partial rows are only 8 (independent) loads deep per thread: this stage is pure latency.
 __global__ static void colsum_kernel(const float* __restrict__ part, int R, int N, float* __restrict__ out) {

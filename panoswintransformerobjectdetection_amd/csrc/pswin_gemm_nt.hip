@@ -56,7 +56,8 @@ template <int BM, int EPI, int S = 2>
 __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(const unsigned short* __restrict__ X, const unsigned short* __restrict__ W,
                                                                  const float* __restrict__ bias, unsigned short* __restrict__ Y,
                                                                  int M, int N, int K, int tiles_m, int tiles_n,
-                                                                 const unsigned short* __restrict__ aux, float* __restrict__ partial) {
+                                                                 const unsigned short* __restrict__ aux, float* __restrict__ partial,
+                                                                 const float* __restrict__ sample_scale, int rows_per_sample) {
     constexpr int RT = BM / 32;                       // 16-row tiles per wave (waves: 2 along M x 2 along N)
     constexpr int WROWS = BM / 2;                     // rows per wave
     constexpr int AJ = BM / 32, BJ = BN / 32;         // 8-row LDS-DMA blocks per wave and k-step (4 waves)
@@ -70,12 +71,45 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(const unsigned s
 
     // tile of this workgroup: contiguous chunks of the tile list per XCD, column tile fastest
     const int ntiles = tiles_m * tiles_n;
-    int t;
-    {
-        const int bid = blockIdx.x, q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, loc = bid / 8;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;       // bijective for any ntiles
+    auto xcd_deal = [](int bid, int n) {
+        const int q = n / 8, r = n % 8, xcd = bid % 8, loc = bid / 8;
+        return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;    // bijective for any n
+    };
+    int tm, tn;
+    if (sample_scale == nullptr) {
+        const int t = xcd_deal(blockIdx.x, ntiles);
+        tm = t / tiles_n;
+        tn = t - tm * tiles_n;
+    } else {
+        // Sample liveness (pswin_common.hpp; the host passes it only for rows_per_sample % BM == 0 and M = B * rows_per_sample): the
+        // tiles of the live samples are COMPACTED into the first tiles_live workgroups and dealt to the XCDs like a launch of that
+        // many tiles -- a dead sample's tiles that merely left early would idle the XCD whose chunk they are while the others run
+        // their full rounds.  The remaining workgroups each settle one dead tile without a load or an MFMA and leave.
+        const int tps = rows_per_sample / BM;                                     // row tiles per sample
+        const unsigned long long live = live_sample_mask(sample_scale, M / rows_per_sample);
+        const int tiles_live = sample_count(live) * tps * tiles_n, bid = blockIdx.x;
+        const bool dead = bid >= tiles_live;
+        const int t = dead ? bid - tiles_live : xcd_deal(bid, tiles_live);
+        const int tmc = t / tiles_n, sc = tmc / tps;                              // row tile / sample among the live (dead) ones
+        tn = t - tmc * tiles_n;
+        tm = kth_sample(dead ? dead_sample_mask(live, M / rows_per_sample) : live, sc) * tps + (tmc - sc * tps);
+        if (dead) {
+            // EPI 0 / 3: the output rows of a dead sample are zeros (row kernels that do not skip read them next); EPI 1: a zero row of
+            // bias-gradient partials, y stays unwritten; EPI 2: nothing -- both outputs stay unwritten and no reader may touch them
+            if constexpr (EPI == 0 || EPI == 3) {
+                constexpr int ROW_CHUNKS = BN * (EPI == 3 ? 4 : 2) / 16;          // 16-byte pieces of a tile row
+                char* yb = reinterpret_cast<char*>(Y);
+                const size_t ld = (size_t)N * (EPI == 3 ? 4 : 2), col = (size_t)tn * BN * (EPI == 3 ? 4 : 2);
+                for (int i = tid; i < BM * ROW_CHUNKS; i += NT_THREADS) {
+                    const int r = i / ROW_CHUNKS, ch = i - r * ROW_CHUNKS, row = tm * BM + r;
+                    if (row < M) *reinterpret_cast<u32x4*>(yb + (size_t)row * ld + col + 16 * ch) = u32x4{0u, 0u, 0u, 0u};
+                }
+            } else if constexpr (EPI == 1) {
+                if (tid < BN) partial[(size_t)tm * N + tn * BN + tid] = 0.f;
+            }
+            return;
+        }
     }
-    const int tm = t / tiles_n, tn = t - tm * tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
 
     // LDS-DMA source addressing: a wave instruction moves 8 rows x 128 B; lane i -> row i / 8, physical chunk i & 7, which
@@ -297,7 +331,8 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(const unsigned s
 }
 
 template <int BM, int EPI, int S>
-int launch_nt_s(const void* x, const void* w, const float* bias, void* y, int M, int N, int K, hipStream_t st, const void* aux, float* partial) {
+int launch_nt_s(const void* x, const void* w, const float* bias, void* y, int M, int N, int K, hipStream_t st, const void* aux, float* partial,
+                const float* sample_scale, int rows_per_sample) {
     constexpr size_t lds = S * (size_t)(BM + BN) * BK * 2;
     static_assert(lds <= 160 * 1024, "LDS");
     static std::atomic<unsigned long long> configured{0};
@@ -305,7 +340,8 @@ int launch_nt_s(const void* x, const void* w, const float* bias, void* y, int M,
     const int tiles_m = (M + BM - 1) / BM, tiles_n = N / BN;
     hipLaunchKernelGGL((gemm_nt_kernel<BM, EPI, S>), dim3(tiles_m * tiles_n), dim3(NT_THREADS), lds, st,
                        reinterpret_cast<const unsigned short*>(x), reinterpret_cast<const unsigned short*>(w), bias,
-                       reinterpret_cast<unsigned short*>(y), M, N, K, tiles_m, tiles_n, reinterpret_cast<const unsigned short*>(aux), partial);
+                       reinterpret_cast<unsigned short*>(y), M, N, K, tiles_m, tiles_n, reinterpret_cast<const unsigned short*>(aux), partial,
+                       sample_scale, sample_scale ? rows_per_sample : 0);
     PSWIN_LAUNCH_RET();
 }
 
@@ -315,10 +351,15 @@ constexpr int DEEP_TILES = 256;
 
 template <int BM, int EPI>
 int launch_nt(const void* x, const void* w, const float* bias, void* y, int M, int N, int K, hipStream_t st, const void* aux = nullptr,
-              float* partial = nullptr) {
+              float* partial = nullptr, const float* sample_scale = nullptr, int rows_per_sample = 0) {
     const int tiles = ((M + BM - 1) / BM) * (N / BN);
-    if (tiles <= DEEP_TILES && K / BK >= 3) return launch_nt_s<BM, EPI, 4>(x, w, bias, y, M, N, K, st, aux, partial);
-    return launch_nt_s<BM, EPI, 2>(x, w, bias, y, M, N, K, st, aux, partial);
+    if (tiles <= DEEP_TILES && K / BK >= 3) return launch_nt_s<BM, EPI, 4>(x, w, bias, y, M, N, K, st, aux, partial, sample_scale, rows_per_sample);
+    return launch_nt_s<BM, EPI, 2>(x, w, bias, y, M, N, K, st, aux, partial, sample_scale, rows_per_sample);
+}
+
+// sample liveness of a launch with tile_m-row tiles: whole tiles per sample, M = B * rows_per_sample, B <= 64 (null: always fine)
+inline bool nt_live_ok(const float* sample_scale, int rows_per_sample, long long M, int tile_m) {
+    return !sample_scale || (rows_per_sample > 0 && rows_per_sample % tile_m == 0 && M % rows_per_sample == 0 && M / rows_per_sample <= LIVE_SAMPLES_MAX);
 }
 
 }  // namespace
@@ -330,15 +371,21 @@ int pswin_gemm_nt_supported(long long M, int K, int N) {
 }
 
 /* tile_m: 0 = choose (128-row tiles unless that leaves the 256 CUs short of two rounds of tiles), or 64 / 96 / 128 */
-int pswin_gemm_nt(const void* x, const void* w, const float* bias, void* y, long long M, int K, int N, int tile_m, void* stream) {
+int pswin_gemm_nt_live(const void* x, const void* w, const float* bias, void* y, long long M, int K, int N, int tile_m,
+                       const float* sample_scale, int rows_per_sample, void* stream) {
     PSWIN_CHECK_ARG(x && w && y && pswin_gemm_nt_supported(M, K, N) && (tile_m == 0 || tile_m == 64 || tile_m == 96 || tile_m == 128));
     PSWIN_CHECK_ARG(aligned16(x) && aligned16(w) && aligned16(y) && aligned16(bias));
     const int m = (int)M;
     if (tile_m == 0) tile_m = ((long long)((m + 127) / 128) * (N / BN) >= 512) ? 128 : 64;
-    if (tile_m == 128) return launch_nt<128, 0>(x, w, bias, y, m, N, K, (hipStream_t)stream);
+    PSWIN_CHECK_ARG(nt_live_ok(sample_scale, rows_per_sample, M, tile_m));
+    if (tile_m == 128) return launch_nt<128, 0>(x, w, bias, y, m, N, K, (hipStream_t)stream, nullptr, nullptr, sample_scale, rows_per_sample);
     // 96-row tiles (plain epilogue only): for row counts whose 64-row tiles need a second, mostly empty round of the 512 tile slots
-    if (tile_m == 96) return launch_nt<96, 0>(x, w, bias, y, m, N, K, (hipStream_t)stream);
-    return launch_nt<64, 0>(x, w, bias, y, m, N, K, (hipStream_t)stream);
+    if (tile_m == 96) return launch_nt<96, 0>(x, w, bias, y, m, N, K, (hipStream_t)stream, nullptr, nullptr, sample_scale, rows_per_sample);
+    return launch_nt<64, 0>(x, w, bias, y, m, N, K, (hipStream_t)stream, nullptr, nullptr, sample_scale, rows_per_sample);
+}
+
+int pswin_gemm_nt(const void* x, const void* w, const float* bias, void* y, long long M, int K, int N, int tile_m, void* stream) {
+    return pswin_gemm_nt_live(x, w, bias, y, M, K, N, tile_m, nullptr, 0, stream);
 }
 
 /* the same product written as f32 (y: f32 [M, N]): for a Linear whose result joins the fp32 residual stream (PatchMerging.reduction) */
@@ -356,21 +403,33 @@ int pswin_gemm_nt_partial_rows(long long M, int tile_m) {
     return (M > 0 && (tile_m == 64 || tile_m == 128)) ? (int)((M + tile_m - 1) / tile_m) : PSWIN_ERR_ARG;
 }
 
-int pswin_gemm_nt_gelu_fwd(const void* x, const void* w, const float* bias, void* pre, void* h, long long M, int K, int N, int tile_m,
-                           void* stream) {
+int pswin_gemm_nt_gelu_fwd_live(const void* x, const void* w, const float* bias, void* pre, void* h, long long M, int K, int N, int tile_m,
+                                const float* sample_scale, int rows_per_sample, void* stream) {
     PSWIN_CHECK_ARG(x && w && bias && pre && h && pswin_gemm_nt_supported(M, K, N) && (tile_m == 64 || tile_m == 128));
     PSWIN_CHECK_ARG(aligned16(x) && aligned16(w) && aligned16(pre) && aligned16(h) && aligned16(bias));
+    PSWIN_CHECK_ARG(nt_live_ok(sample_scale, rows_per_sample, M, tile_m));
     float* b = const_cast<float*>(bias);
-    if (tile_m == 128) return launch_nt<128, 2>(x, w, nullptr, pre, (int)M, N, K, (hipStream_t)stream, h, b);
-    return launch_nt<64, 2>(x, w, nullptr, pre, (int)M, N, K, (hipStream_t)stream, h, b);
+    if (tile_m == 128) return launch_nt<128, 2>(x, w, nullptr, pre, (int)M, N, K, (hipStream_t)stream, h, b, sample_scale, rows_per_sample);
+    return launch_nt<64, 2>(x, w, nullptr, pre, (int)M, N, K, (hipStream_t)stream, h, b, sample_scale, rows_per_sample);
+}
+
+int pswin_gemm_nt_gelu_fwd(const void* x, const void* w, const float* bias, void* pre, void* h, long long M, int K, int N, int tile_m,
+                           void* stream) {
+    return pswin_gemm_nt_gelu_fwd_live(x, w, bias, pre, h, M, K, N, tile_m, nullptr, 0, stream);
+}
+
+int pswin_gemm_nt_gelu_bwd_live(const void* dy, const void* w_t, const void* pre, const float* bias, void* dpre, float* partial, long long M,
+                                int K, int N, int tile_m, const float* sample_scale, int rows_per_sample, void* stream) {
+    PSWIN_CHECK_ARG(dy && w_t && pre && dpre && partial && pswin_gemm_nt_supported(M, K, N) && (tile_m == 64 || tile_m == 128));
+    PSWIN_CHECK_ARG(aligned16(dy) && aligned16(w_t) && aligned16(pre) && aligned16(dpre) && aligned16(bias) && aligned16(partial));
+    PSWIN_CHECK_ARG(nt_live_ok(sample_scale, rows_per_sample, M, tile_m));
+    if (tile_m == 128) return launch_nt<128, 1>(dy, w_t, bias, dpre, (int)M, N, K, (hipStream_t)stream, pre, partial, sample_scale, rows_per_sample);
+    return launch_nt<64, 1>(dy, w_t, bias, dpre, (int)M, N, K, (hipStream_t)stream, pre, partial, sample_scale, rows_per_sample);
 }
 
 int pswin_gemm_nt_gelu_bwd(const void* dy, const void* w_t, const void* pre, const float* bias, void* dpre, float* partial, long long M,
                            int K, int N, int tile_m, void* stream) {
-    PSWIN_CHECK_ARG(dy && w_t && pre && dpre && partial && pswin_gemm_nt_supported(M, K, N) && (tile_m == 64 || tile_m == 128));
-    PSWIN_CHECK_ARG(aligned16(dy) && aligned16(w_t) && aligned16(pre) && aligned16(dpre) && aligned16(bias) && aligned16(partial));
-    if (tile_m == 128) return launch_nt<128, 1>(dy, w_t, bias, dpre, (int)M, N, K, (hipStream_t)stream, pre, partial);
-    return launch_nt<64, 1>(dy, w_t, bias, dpre, (int)M, N, K, (hipStream_t)stream, pre, partial);
+    return pswin_gemm_nt_gelu_bwd_live(dy, w_t, pre, bias, dpre, partial, M, K, N, tile_m, nullptr, 0, stream);
 }
 
 }  // extern "C"

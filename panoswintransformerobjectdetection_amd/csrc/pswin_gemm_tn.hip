@@ -91,20 +91,23 @@ struct TnJob {
     const unsigned short* x;
     void* part;
     float* db;
-    int M, N, K, tiles_k, tiles_n, rows_per_split, zero_lo, zero_hi;
-    int first_wg, n_wg, flags, xmap;                   // flags = out_bf16 | splits << 1;  xmap = g | gn << 8 | bk << 16 | bn << 24 (below)
+    const float* sample_scale;                         // sample liveness (pswin_common.hpp) or null = every row is contracted
+    int M, N, K, rows_per_split, zero_lo, zero_hi;
+    int first_wg, flags, xmap, rows_per_sample;        // flags = out_bf16 | splits << 1;  xmap = g | gn << 8 | bk << 16 | bn << 24 (below)
 };
 constexpr int TN_JOBS_MAX = 48;                        // 48 x 80 B: the kernel-argument segment holds 4 KB
 struct TnBatch {
     TnJob job[TN_JOBS_MAX];
     int n;
 };
+// (the tile counts are derived in the kernel and a job's workgroup count is implied by its split count: that made room for the liveness)
+static_assert(sizeof(TnJob) == 80 && sizeof(TnBatch) <= 4000, "the job table travels in the 4 KB kernel-argument segment");
 
 template <int WK, int WN, int STAGES>
 __global__ __launch_bounds__(RING_THREADS, 2) void gemm_tn_ring_kernel(const TnBatch batch) {
     using G = RingGeom<WK, WN, STAGES>;
     // this workgroup's job: first_wg ascending (multiples of 8, so that a job's workgroups keep the round-robin XCD pattern of a launch
-    // of its own); workgroups past a job's count are padding and leave at once
+    // of its own)
     int jlo = 0, jhi = batch.n - 1;
     while (jlo < jhi) {
         const int mid = (jlo + jhi + 1) >> 1;
@@ -113,12 +116,12 @@ __global__ __launch_bounds__(RING_THREADS, 2) void gemm_tn_ring_kernel(const TnB
     }
     const TnJob& job = batch.job[jlo];
     const int jbid = (int)blockIdx.x - job.first_wg;
-    if (jbid >= job.n_wg) return;
     const unsigned short* __restrict__ DY = job.dy;
     const unsigned short* __restrict__ X = job.x;
     void* __restrict__ P = job.part;
     float* __restrict__ DB = job.db;
-    const int M = job.M, N = job.N, K = job.K, tiles_k = job.tiles_k, tiles_n = job.tiles_n, rows_per_split = job.rows_per_split;
+    const int M = job.M, N = job.N, K = job.K, rows_per_split = job.rows_per_split;
+    const int tiles_k = (K + 96 * WK - 1) / (96 * WK), tiles_n = (N + 48 * WN - 1) / (48 * WN);
     const int zero_lo = job.zero_lo, zero_hi = job.zero_hi;
     const bool out_bf16 = (job.flags & 1) != 0;
     constexpr int IA = 6, JB = 3;                      // 16-wide tiles per wave along k (96 columns) / n (48 columns)
@@ -152,6 +155,27 @@ __global__ __launch_bounds__(RING_THREADS, 2) void gemm_tn_ring_kernel(const TnB
         const int left = (M - m_begin + MSTEP - 1) / MSTEP;           // slabs that hold at least one real row
         steps = left < steps ? (left > 0 ? left : 0) : steps;
     }
+    // Sample liveness: of the range's `steps` (<= 64 then: tn_job_ok) slabs only those that hold a row of a live sample are contracted
+    // (a slab that straddles a live and a dead sample is kept: its dead rows of dY are zeros).  Lane l looks at slab l of the range and
+    // one ballot gives the live slabs as a 64-bit scalar mask; the ring asks for its slabs in ascending order, so issue() takes the
+    // mask's lowest bit each time.  `steps` becomes the count of live slabs, and nothing else of the loop below changes.
+    const float* __restrict__ SS = job.sample_scale;
+    unsigned long long live_slabs = 0ull;
+    if (SS != nullptr) {
+        const int rows_per_sample = job.rows_per_sample;
+        const unsigned long long live_samples = live_sample_mask(SS, M / rows_per_sample);
+        bool live = false;
+        if (lane < steps) {
+            const int r0 = m_begin + lane * MSTEP, r1 = (r0 + MSTEP < M ? r0 + MSTEP : M) - 1;
+            const int s0 = r0 / rows_per_sample, s1 = r1 / rows_per_sample;
+            const unsigned long long span = s1 - s0 >= 63 ? ~0ull : (2ull << (s1 - s0)) - 1ull;
+            live = ((live_samples >> s0) & span) != 0ull;
+        }
+        const unsigned long long b = __ballot(live);
+        live_slabs = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b) |
+                     (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32)) << 32;
+        steps = __builtin_popcountll(live_slabs);
+    }
 
     // LDS-DMA: PANELS x 8 row blocks (8 rows x 128 B) per slab = PANELS blocks per wave: wave w brings blocks w * PANELS .. of the
     // list [X panels | dY panels]; PANELS is 6 or 8 and PX * 8 a multiple of it, so a wave serves one operand; rows past M read as
@@ -177,7 +201,12 @@ __global__ __launch_bounds__(RING_THREADS, 2) void gemm_tn_ring_kernel(const TnB
     }
     auto issue = [&](int step, int stage) {
         char* base = smem + stage * RING_STAGE_BYTES + wave * LOADS * 1024;
-        const unsigned m = (unsigned)(m_begin + step * MSTEP) * ld2;
+        int slab = step;
+        if (SS != nullptr) {                              // the step-th live slab: issue() is called with step = 0, 1, 2, ...
+            slab = __builtin_ctzll(live_slabs);
+            live_slabs &= live_slabs - 1ull;
+        }
+        const unsigned m = (unsigned)(m_begin + slab * MSTEP) * ld2;
 #pragma unroll
         for (int j = 0; j < LOADS; ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(src, (lds_void*)(base + j * 1024), 16, goff[j] + m, 0, 0, 0);
     };
@@ -342,7 +371,9 @@ int launch_tn_batch(const TnBatch& b, int wgs, hipStream_t st) {
 inline bool tn_job_ok(const pswin_tn_job& q) {
     return q.dy && q.x && q.partial && q.M >= 64 && (q.M + 64) * (long long)(q.K > q.N ? q.K : q.N) * 2 < 0xFFFFFF00ll && ring_geom(q.N, q.K) >= 0 &&
            q.splits >= 1 && q.splits <= q.M / 64 && valid_dtype(q.partial_dtype) && aligned16(q.dy) && aligned16(q.x) && aligned16(q.partial) &&
-           q.zero_lo >= 0 && q.zero_hi >= q.zero_lo && q.zero_hi <= q.N;
+           q.zero_lo >= 0 && q.zero_hi >= q.zero_lo && q.zero_hi <= q.N &&
+           (!q.sample_scale || (q.rows_per_sample > 0 && q.M % q.rows_per_sample == 0 && q.M / q.rows_per_sample <= LIVE_SAMPLES_MAX &&
+                                (q.M + q.splits - 1) / q.splits <= 64 * MSTEP));      // one 64-bit mask of live slabs per row range
 }
 
 // every job of `geom` in the caller's order, <= TN_JOBS_MAX per launch; the caller lists the longest row ranges first (the hardware
@@ -373,12 +404,14 @@ int launch_tn_jobs(const pswin_tn_job* jobs, int n_jobs, int geom, hipStream_t s
         j.M = (int)q.M;
         j.N = q.N;
         j.K = q.K;
-        j.tiles_k = (q.K + tk - 1) / tk;
-        j.tiles_n = (q.N + tn - 1) / tn;
+        const int tiles_k = (q.K + tk - 1) / tk, tiles_n = (q.N + tn - 1) / tn;
+        j.sample_scale = q.sample_scale;
+        j.rows_per_sample = q.sample_scale ? q.rows_per_sample : 0;
         j.rows_per_split = (int)(((q.M + q.splits - 1) / q.splits + MSTEP - 1) / MSTEP * MSTEP);
         j.zero_lo = q.zero_lo;
         j.zero_hi = q.zero_hi;
         j.first_wg = (int)wgs;
+        int n_wg;
         {
             // XCDs per split and the cut of its tile grid (kernel comment): cost of a cut = operand columns fetched by the g XCDs
             const int S = q.splits;
@@ -392,16 +425,16 @@ int launch_tn_jobs(const pswin_tn_job* jobs, int n_jobs, int geom, hipStream_t s
             long long best = -1;
             for (int gn = 1; gn <= g; gn *= 2) {
                 const int gk = g / gn;
-                const long long cost = (long long)((j.tiles_k + gk - 1) / gk) * tk + (long long)((j.tiles_n + gn - 1) / gn) * tn;
+                const long long cost = (long long)((tiles_k + gk - 1) / gk) * tk + (long long)((tiles_n + gn - 1) / gn) * tn;
                 if (best < 0 || cost < best) best = cost, best_gn = gn;
             }
-            const int gn = best_gn, gk = g / gn, bk = (j.tiles_k + gk - 1) / gk, bn = (j.tiles_n + gn - 1) / gn;
+            const int gn = best_gn, gk = g / gn, bk = (tiles_k + gk - 1) / gk, bn = (tiles_n + gn - 1) / gn;
             const int lanes = 8 / g, rounds = (S + lanes - 1) / lanes;
             j.xmap = g | gn << 8 | bk << 16 | bn << 24;
-            j.n_wg = 8 * rounds * bk * bn;
+            n_wg = 8 * rounds * bk * bn;
         }
         j.flags = (q.partial_dtype == PSWIN_BF16 ? 1 : 0) | q.splits << 1;
-        wgs += j.n_wg;
+        wgs += n_wg;
         if (++b.n == TN_JOBS_MAX || wgs > (1ll << 24)) {
             if (const int rc = flush()) return rc;
         }
@@ -429,6 +462,8 @@ int pswin_gemm_tn_ring_splits(long long M, int N, int K, int target_wgs) {
     return s < 1 ? 1 : s;
 }
 
+int pswin_gemm_tn_ring_table_bytes(void) { return (int)sizeof(TnBatch); }
+
 int pswin_gemm_tn_ring_jobs(const pswin_tn_job* jobs, int n_jobs, void* stream) {
     PSWIN_CHECK_ARG(jobs && n_jobs > 0);
     for (int i = 0; i < n_jobs; ++i) PSWIN_CHECK_ARG(tn_job_ok(jobs[i]));
@@ -451,6 +486,8 @@ int pswin_gemm_tn_ring_bias(const void* dy, const void* x, void* partial, int pa
     q.partial_dtype = partial_dtype;
     q.zero_lo = zero_lo;
     q.zero_hi = zero_hi;
+    q.sample_scale = nullptr;
+    q.rows_per_sample = 0;
     return pswin_gemm_tn_ring_jobs(&q, 1, stream);
 }
 

@@ -36,7 +36,9 @@ class Reduction(NamedTuple):
 
 
 class WeightGrad(NamedTuple):
-    """partial[s] = dy[rows of split s]^T x, and dbias_partial[s] = the column sums of those rows of dy if given (_lib.TnJob)"""
+    """partial[s] = dy[rows of split s]^T x, and dbias_partial[s] = the column sums of those rows of dy if given (_lib.TnJob).
+    sample_scale / rows_per_sample: the sample liveness of the rows (include/pswin.h) or None / 0; the record keeps the factor vector
+    referenced until the launch, like the operands."""
     dy: torch.Tensor
     x: torch.Tensor
     partial: torch.Tensor
@@ -47,6 +49,8 @@ class WeightGrad(NamedTuple):
     splits: int
     zero_lo: int
     zero_hi: int
+    sample_scale: Optional[torch.Tensor] = None
+    rows_per_sample: int = 0
 
     @property
     def ref(self):
@@ -55,6 +59,7 @@ class WeightGrad(NamedTuple):
     def fill(self, a):
         a.dy, a.x, a.partial, a.dbias_partial = self.dy.data_ptr(), self.x.data_ptr(), self.partial.data_ptr(), _addr(self.dbias_partial)
         a.M, a.N, a.K, a.splits, a.partial_dtype, a.zero_lo, a.zero_hi = self.M, self.N, self.K, self.splits, dtype_code(self.partial), self.zero_lo, self.zero_hi
+        a.sample_scale, a.rows_per_sample = _addr(self.sample_scale), self.rows_per_sample if self.sample_scale is not None else 0
 
 
 class TableGrad(NamedTuple):
@@ -114,6 +119,12 @@ def _wgrad_traffic(jobs):
     return dict(algo_bytes=nbytes, algo_flops=flops, timed_as="pswin_gemm_tn_ring", partial_bytes=pbytes)
 
 
+def weight_grad(dy, x, partial, dbias_partial, splits, zero_lo=0, zero_hi=0, live=None):
+    """The WeightGrad record of dy^T x; live: None or (sample_scale f32 [B] on the device, rows_per_sample)."""
+    scale, rps = (None, 0) if live is None else (live[0], int(live[1]))
+    return WeightGrad(dy, x, partial, dbias_partial, dy.shape[0], dy.shape[1], x.shape[1], splits, zero_lo, zero_hi, scale, rps)
+
+
 def _launch_wgrads(jobs):
     """The queued weight gradients as ONE pswin_gemm_tn_ring_jobs call per device (one kernel launch per tile geometry): longest row
     ranges first, so that the tail of the launch is made of the short ones."""
@@ -131,9 +142,9 @@ class _PassQueue:
     def add_reduction(self, src, rows, cols, dst, ld=None, offset=0):
         self.reductions.append(Reduction(src, offset, dtype_code(src), rows, cols, cols if ld is None else ld, dst))
 
-    def add_weight_gradient(self, dy, x, partial, dbias_partial, splits, zero_lo=0, zero_hi=0):
-        """The operands stay referenced by the queue until the launch."""
-        self.wgrads.append(WeightGrad(dy, x, partial, dbias_partial, dy.shape[0], dy.shape[1], x.shape[1], splits, zero_lo, zero_hi))
+    def add_weight_gradient(self, dy, x, partial, dbias_partial, splits, zero_lo=0, zero_hi=0, live=None):
+        """The operands (and the factor vector of live = (sample_scale, rows_per_sample)) stay referenced by the queue until the launch."""
+        self.wgrads.append(weight_grad(dy, x, partial, dbias_partial, splits, zero_lo, zero_hi, live))
 
     def add_table_gradient(self, job, partial_sums):
         """job: a TableGrad; partial_sums: the Reduction between its two stages."""

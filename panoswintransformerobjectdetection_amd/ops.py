@@ -39,6 +39,9 @@ FUSED_GELU_BWD = _on("fused_gelu_bwd")
 FUSED_MLP = _on("fused_mlp")
 # off: the dScore-tile sums of an attention module run inside its backward instead of in one launch at the end of the pass
 DEFER_TABLE_PARTIALS = _on("defer_table_partials")
+# per-sample DropPath: the tiled GEMMs of the Mlp and the weight-gradient launch leave out the rows of the samples whose branch was
+# dropped (factor 0: the branch output is multiplied by zero and every gradient into it is an exact zero); off: everything is computed
+SAMPLE_SKIP = _on("sample_skip")
 
 
 def _dev_key(device):
@@ -704,10 +707,10 @@ def grouped_wgrad_splits(M):
     return max(1, min(M // 64, s))
 
 
-def queue_weight_gradient(dy, x, weight, bias, zero_cols):
+def queue_weight_gradient(dy, x, weight, bias, zero_cols, live=None):
     """dW = dy^T x (and the bias gradient, the column sums of dy) through the grouped end-of-pass launch, if this backward pass may
     postpone them (see set_deferred_reductions): returns (dw f32 [N, K], db f32 [N] or None) -- tensors that are FILLED when the pass
-    ends -- or None = launch now.  The operands stay referenced by the queue until then."""
+    ends -- or None = launch now.  The operands stay referenced by the queue until then.  live: the rows' sample liveness (wgrad_live)."""
     M, N = dy.shape
     K = x.shape[1]
     if not (GROUPED_WGRAD and dy.dtype == torch.bfloat16 and gemm_tn_ring_splits(M, N, K) > 0):
@@ -733,7 +736,7 @@ def queue_weight_gradient(dy, x, weight, bias, zero_cols):
             q.add_reduction(dbp, splits, N, db)
         db = db.view(N)                                   # fresh views: see sum_rows
     zlo, zhi = (0, 0) if zero_cols is None else (int(zero_cols[0]), int(zero_cols[1]))
-    q.add_weight_gradient(dy, x, part, dbp, splits, zlo, zhi)
+    q.add_weight_gradient(dy, x, part, dbp, splits, zlo, zhi, wgrad_live(live, M, splits))
     return out.view(N, K), db
 
 
@@ -749,7 +752,27 @@ def gemm_tn_ring_splits(M, N, K):
     return int(_lib.load().pswin_gemm_tn_ring_splits(M, N, K, 0))
 
 
-def gemm_tn_ring(dy, x, splits, out_dtype=torch.float32, bias_sums=False, zero_cols=None):
+def sample_liveness(scale, rows_per_sample, M):
+    """The liveness argument (sample_scale f32 [B] contiguous on the device, rows_per_sample) of a kernel over M sample-major rows, or
+    None: no factor vector (no DropPath in this pass), the switch is off, or the rows are not B <= 64 whole samples."""
+    if scale is None or not SAMPLE_SKIP or rows_per_sample <= 0 or M % rows_per_sample or not 0 < M // rows_per_sample <= 64:
+        return None
+    if scale.dtype != torch.float32 or scale.numel() != M // rows_per_sample:
+        return None
+    return scale.detach().contiguous(), int(rows_per_sample)
+
+
+def wgrad_live_rows_ok(M, splits):
+    """the ring kernel keeps the live 64-row slabs of a workgroup's row range in one 64-bit mask (csrc/pswin_gemm_tn.hip)"""
+    return splits > 0 and -(-M // splits) <= 64 * 64
+
+
+def wgrad_live(live, M, splits):
+    """`live` if the ring kernel takes it for a weight gradient over M rows in `splits` row ranges, else None"""
+    return live if live is not None and wgrad_live_rows_ok(M, splits) else None
+
+
+def gemm_tn_ring(dy, x, splits, out_dtype=torch.float32, bias_sums=False, zero_cols=None, live=None):
     """[splits, N, K] partial sums of dy^T x over `splits` row ranges (dy [M, N], x [M, K] bf16) in f32 or bf16.
     Roofline bookkeeping: algorithmic bytes = dY and X read once + the f32 gradient written once, 2 (MK + MN) + 4 NK; the
     split partial slabs are an implementation artefact and are reported separately (partial_bytes), never as algorithmic traffic.
@@ -759,6 +782,12 @@ def gemm_tn_ring(dy, x, splits, out_dtype=torch.float32, bias_sums=False, zero_c
     M, N = dy.shape
     K = x.shape[1]
     part = torch.empty(splits, N, K, dtype=out_dtype, device=x.device)
+    live = wgrad_live(live, M, splits)
+    if live is not None:                                  # the one-product entry points take no liveness: a one-entry job table
+        dbp = torch.empty(splits, N, dtype=torch.float32, device=x.device) if bias_sums else None
+        zlo, zhi = (0, 0) if zero_cols is None else (int(zero_cols[0]), int(zero_cols[1]))
+        grad_queue._launch_wgrads([grad_queue.weight_grad(dy, x, part, dbp, int(splits), zlo, zhi, live)])
+        return (part, dbp) if bias_sums else part
     if not bias_sums:
         call("pswin_gemm_tn_ring", x, ptr(dy), ptr(x), ptr(part), dtype_code(part), M, N, K, int(splits),
              algo_bytes=2 * (M * K + M * N) + 4 * N * K, algo_flops=2 * M * K * N, partial_bytes=part.element_size() * splits * N * K)
@@ -771,8 +800,10 @@ def gemm_tn_ring(dy, x, splits, out_dtype=torch.float32, bias_sums=False, zero_c
     return part, dbp
 
 
-def gemm_nt(x2d, w, bias=None, tile_m=0, out_f32=False):
-    """y = x2d @ w^T (+ bias): x2d [M, K] bf16, w [N, K] bf16, bias f32 [N] or None -> [M, N] bf16 (out_f32: f32, pswin_gemm_nt_f32)."""
+def gemm_nt(x2d, w, bias=None, tile_m=0, out_f32=False, live=None):
+    """y = x2d @ w^T (+ bias): x2d [M, K] bf16, w [N, K] bf16, bias f32 [N] or None -> [M, N] bf16 (out_f32: f32, pswin_gemm_nt_f32).
+    live = (sample_scale, rows_per_sample), bf16 result only: the rows of dead samples are not read and come out as zeros
+    (pswin_gemm_nt_live; rows_per_sample must be a multiple of tile_m)."""
     x2d, w = x2d.contiguous(), w.contiguous()
     M, K = x2d.shape
     N = w.shape[0]
@@ -783,6 +814,10 @@ def gemm_nt(x2d, w, bias=None, tile_m=0, out_f32=False):
              algo_bytes=2 * (M * K + N * K) + 4 * M * N, algo_flops=2 * M * K * N)
         return y
     y = torch.empty(M, N, dtype=torch.bfloat16, device=x2d.device)
+    if live is not None:                                  # (booked as the full problem, like every launch that skips dead samples)
+        call("pswin_gemm_nt_live", x2d, ptr(x2d), ptr(w), ptr(b), ptr(y), M, K, N, int(tile_m), ptr(live[0]), live[1],
+             timed_as="pswin_gemm_nt", algo_bytes=2 * (M * K + M * N + N * K), algo_flops=2 * M * K * N)
+        return y
     call("pswin_gemm_nt", x2d, ptr(x2d), ptr(w), ptr(b), ptr(y), M, K, N, int(tile_m),
          algo_bytes=2 * (M * K + M * N + N * K), algo_flops=2 * M * K * N)
     return y
@@ -818,7 +853,7 @@ def skinny_gemm(x2d, w, bias=None, transpose_w=False):
     return y
 
 
-def linear_product(x2d, wb, bias=None, b_lp=None, out_f32=False, skinny=False):
+def linear_product(x2d, wb, bias=None, b_lp=None, out_f32=False, skinny=False, live=None):
     """y = x2d @ wb^T (+ bias) on the first kernel that takes the shape: the streaming GEMM (skinny=True; the stage-0 shapes), the
     tiled HIP GEMM where gemm_nt_tile picks it (stages 1-3), else the library GEMM (with b_lp, bias's bf16 copy, if given).
     out_f32: an f32 result where the tiled HIP GEMM runs (its epilogue writes it), a cast of the bf16 result elsewhere."""
@@ -829,7 +864,9 @@ def linear_product(x2d, wb, bias=None, b_lp=None, out_f32=False, skinny=False):
         return y.float() if out_f32 else y
     tile = gemm_nt_tile(M, K, N, "pswin_gemm_nt_f32" if out_f32 else "pswin_gemm_nt") if x2d.dtype == torch.bfloat16 else 0
     if tile:
-        return gemm_nt(x2d, wb, bias, tile, out_f32=out_f32)
+        return gemm_nt(x2d, wb, bias, tile, out_f32=out_f32, live=live)
+    if live is not None:
+        raise PswinError("linear_product: sample liveness needs the tiled HIP GEMM (mlp_sample_skip decides that before the call)")
     bb = None if bias is None else (b_lp if b_lp is not None else bias.to(x2d.dtype))
     with _lib.timed("lib_gemm_fwd", 2 * (M * K + M * N + N * K), 2 * M * K * N):
         y = F.linear(x2d, wb, bb)
@@ -856,7 +893,7 @@ class _LinearSplitK(torch.autograd.Function):
     explicit split-K, 55-75 us) whose fp32 partial sum also removes the bf16 -> fp32 gradient cast."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, w_lp, b_lp, zero_bias_cols=None, w_lp_t=None, out_f32=False):
+    def forward(ctx, x, weight, bias, w_lp, b_lp, zero_bias_cols=None, w_lp_t=None, out_f32=False, live=None):
         # w_lp / b_lp: this step's bf16 copies of the fp32 master parameters (refreshed by ONE multi-tensor cast per
         # forward, see SimplePanoSwinTransformer._refresh_lowp); gradients go to the fp32 masters.
         wb = w_lp if w_lp is not None else weight.to(x.dtype)
@@ -864,6 +901,7 @@ class _LinearSplitK(torch.autograd.Function):
         ctx.has_bias = bias is not None
         ctx.zero_bias_cols = zero_bias_cols
         ctx.weight, ctx.bias = weight, bias                 # for grad_slot / owners: dW may be summed straight into its flat slot
+        ctx.live = live                                     # sample liveness of the rows: the weight gradient leaves dead samples out
         return linear_product(x, wb, bias, b_lp, out_f32, skinny=True)
 
     @staticmethod
@@ -872,14 +910,16 @@ class _LinearSplitK(torch.autograd.Function):
         if dy.dtype != x.dtype:                             # out_f32: the gradient arrives in fp32
             dy = dy.to(x.dtype)
         dx, dw, db = linear_backward(x, wb, dy, ctx.weight, ctx.bias if ctx.has_bias else None, ctx.zero_bias_cols,
-                                     ctx.needs_input_grad[0], wbt)
-        return dx, dw, db, None, None, None, None, None
+                                     ctx.needs_input_grad[0], wbt, wgrad_live=ctx.live)
+        return dx, dw, db, None, None, None, None, None, None
 
 
-def linear_backward(x, wb, dy, weight, bias, zero_bias_cols, need_dx, wbt=None):
+def linear_backward(x, wb, dy, weight, bias, zero_bias_cols, need_dx, wbt=None, wgrad_live=None, dgrad_live=None):
     """Gradients of y = x wb^T (+ bias) for bf16 rows x [M, K], wb [N, K]: (dx or None, dW f32 [N, K], dbias f32 [N] or
     None).  weight / bias: the fp32 master parameters the gradients belong to (grad_slot / deferred reductions).
-    wbt: wb^T [K, N] if the caller keeps one (dx then runs on pswin_gemm_nt where that is the faster kernel)."""
+    wbt: wb^T [K, N] if the caller keeps one (dx then runs on pswin_gemm_nt where that is the faster kernel).
+    wgrad_live / dgrad_live: the rows' sample liveness for the weight gradient / the data gradient (the latter only where the caller
+    knows that dx runs on the tiled GEMM with whole tiles per sample: mlp_sample_skip)."""
     dy = dy.contiguous()
     M, N = dy.shape
     K = x.shape[1]
@@ -891,15 +931,17 @@ def linear_backward(x, wb, dy, weight, bias, zero_bias_cols, need_dx, wbt=None):
         if K == 96 and N in (96, 288, 384) and skinny_gemm_supported(dy, K):
             dx = skinny_gemm(dy, wb, None, transpose_w=True)
         elif tile:
-            dx = gemm_nt(dy, wbt, None, tile)
+            dx = gemm_nt(dy, wbt, None, tile, live=dgrad_live)
         else:
+            if dgrad_live is not None:
+                raise PswinError("linear_backward: sample liveness of the data gradient needs the tiled HIP GEMM")
             with _lib.timed("lib_gemm_dgrad", 2 * (M * K + M * N + N * K), 2 * M * K * N):
                 dx = dy @ wb
-    queued = queue_weight_gradient(dy, x, weight, bias, zero_bias_cols)
-    return (dx, *(queued if queued is not None else weight_gradient(dy, x, weight, bias, zero_bias_cols)))
+    queued = queue_weight_gradient(dy, x, weight, bias, zero_bias_cols, wgrad_live)
+    return (dx, *(queued if queued is not None else weight_gradient(dy, x, weight, bias, zero_bias_cols, wgrad_live)))
 
 
-def weight_gradient(dy, x, weight, bias=None, zero_bias_cols=None):
+def weight_gradient(dy, x, weight, bias=None, zero_bias_cols=None, live=None):
     """dW = dy^T x (f32 [N, K]) and the bias gradient (f32 [N] or None), launched now: the ring kernel (the bias gradient rides along),
     else the library's batched GEMM over row chunks or a plain GEMM; a split's partial slabs summed by sum_rows.  weight / bias: the
     fp32 master parameters the gradients belong to (grad_slot / deferred reductions)."""
@@ -911,9 +953,9 @@ def weight_gradient(dy, x, weight, bias=None, zero_bias_cols=None):
     if rs:                                                   # the ring-pipelined HIP weight-gradient kernel; the bias gradient rides along
         pdt = torch.bfloat16 if (GEMM_TN_RING_BF16 and rs > 1) else torch.float32
         if bias is not None and GEMM_TN_RING_BIAS:
-            part, db_part = gemm_tn_ring(dy, x, rs, pdt, bias_sums=True, zero_cols=zero_bias_cols)
+            part, db_part = gemm_tn_ring(dy, x, rs, pdt, bias_sums=True, zero_cols=zero_bias_cols, live=live)
         else:
-            part = gemm_tn_ring(dy, x, rs, pdt)
+            part = gemm_tn_ring(dy, x, rs, pdt, live=live)
         ch, sp = rs, rs
     else:
         ch = _pick_split(M, -(-N // 64) * -(-K // 64))
@@ -935,16 +977,19 @@ def weight_gradient(dy, x, weight, bias=None, zero_bias_cols=None):
     return dw, db
 
 
-def linear(x, lin, cd, use_bias=True, zero_bias_cols=None, out_f32=False):
+def linear(x, lin, cd, use_bias=True, zero_bias_cols=None, out_f32=False, live=None):
     """nn.Linear on rows.  fp32: F.linear (parity path).  bf16: split-K weight gradient, fp32 parameter gradients.
     use_bias=False: the caller applies lin.bias itself (fused into the next row kernel).  zero_bias_cols=(lo, hi): output
-    columns whose gradient sums to zero over the rows (their bias gradient is zero; the column sum skips them)."""
+    columns whose gradient sums to zero over the rows (their bias gradient is zero; the column sum skips them).
+    live: the rows' sample liveness (sample_liveness) when the gradient of dropped samples' rows is an exact zero (the Linear sits inside a
+    DropPath branch): the weight gradient leaves those rows out."""
     if cd == torch.float32:
         return F.linear(x.float(), lin.weight, lin.bias if use_bias else None)
     shp = x.shape
     w_lp, b_lp, w_lp_t = _lowp(lin)
     return _LinearSplitK.apply(x.to(cd).reshape(-1, shp[-1]), lin.weight, lin.bias if use_bias else None, w_lp,
-                               b_lp if use_bias else None, zero_bias_cols, w_lp_t, out_f32).view(*shp[:-1], lin.weight.shape[0])
+                               b_lp if use_bias else None, zero_bias_cols, w_lp_t, out_f32,
+                               live).view(*shp[:-1], lin.weight.shape[0])
 
 
 def _lowp(lin):
@@ -1105,7 +1150,7 @@ def bias_gelu_backward(y, dh, b, bias):
     return dy, (sum_rows(ws, lib.pswin_bias_gelu_partial_rows(M, N, dtype_code(y)), N, owners=(bias,)) if b is not None else None)
 
 
-def gelu_data_gradient(dout, wb, wbt, pre, b, b1):
+def gelu_data_gradient(dout, wb, wbt, pre, b, b1, live=None):
     """Backward of out = gelu(pre + b) @ wb^T (fc2 without its bias over fc1's bias + GELU) as far as pre: (dL/dpre, fc1's bias gradient
     f32 [N] or None without b).  dout [M, C], wb [C, N], pre [M, N] bf16; b: the f32 bias the forward pass added, b1 its parameter.
     wbt = wb^T: fc2's data gradient, the GELU backward and the bias-gradient partial rows in ONE kernel (pswin_gemm_nt_gelu_bwd);
@@ -1120,6 +1165,10 @@ def gelu_data_gradient(dout, wb, wbt, pre, b, b1):
     dpre = torch.empty_like(pre)
     rows = _lib.load().pswin_gemm_nt_partial_rows(M, tile)
     ws = torch.empty(rows, N, dtype=torch.float32, device=pre.device)
+    if live is not None:         # dead samples: zero rows of bias partials, their rows of dpre stay UNWRITTEN (mlp_sample_skip)
+        call("pswin_gemm_nt_gelu_bwd_live", pre, ptr(dout), ptr(wbt), ptr(pre), ptr(b), ptr(dpre), ptr(ws), M, C, N, tile, ptr(live[0]), live[1],
+             timed_as="pswin_gemm_nt_gelu_bwd", algo_bytes=2 * (M * C + 2 * M * N + N * C), algo_flops=2 * M * N * C)
+        return dpre, (sum_rows(ws, rows, N, owners=(b1,)) if b is not None else None)
     call("pswin_gemm_nt_gelu_bwd", pre, ptr(dout), ptr(wbt), ptr(pre), ptr(b), ptr(dpre), ptr(ws), M, C, N, tile,
          algo_bytes=2 * (M * C + 2 * M * N + N * C), algo_flops=2 * M * N * C)
     return dpre, (sum_rows(ws, rows, N, owners=(b1,)) if b is not None else None)
@@ -1160,14 +1209,56 @@ class _BiasGeluLinear(torch.autograd.Function):
         return dpre.view_as(y2), db, dw, None, None
 
 
+class MlpSkip:
+    """Which products of one _MlpFused call leave out the dead samples' rows (mlp_sample_skip): fwd = fc1 + GELU and fc2 of the forward
+    pass, gelu_bwd = fc2's data gradient + GELU backward, dgrad = fc1's data gradient, dw1 / dw2 = the two weight gradients."""
+    __slots__ = ("fwd", "gelu_bwd", "dgrad", "dw1", "dw2")
+
+    def __init__(self, fwd=False, gelu_bwd=False, dgrad=False, dw1=False, dw2=False):
+        self.fwd, self.gelu_bwd, self.dgrad, self.dw1, self.dw2 = fwd, gelu_bwd, dgrad, dw1, dw2
+
+    def __repr__(self):
+        return "MlpSkip(" + ", ".join(f"{k}={getattr(self, k)}" for k in self.__slots__) + ")"
+
+
+def mlp_sample_skip(M, C, hidden, rows_per_sample, transposed=(True, True), need_dx=True):
+    """The ONE decision per _MlpFused call ([M, C] rows of B = M / rows_per_sample samples, hidden columns inside) about sample
+    skipping.  A product that skips a dead sample in the forward pass leaves that sample's rows of `pre` and `h` UNWRITTEN, and the GELU
+    backward leaves its rows of d(pre) unwritten: whatever torch.empty returned stays there, possibly NaN patterns, and 0 x NaN = NaN.
+    Those three tensors never leave the node, so the rule is that every reader skips exactly the same rows:
+      * fwd: only if ALL six products can skip exactly -- the four GEMMs run on pswin_gemm_nt with whole row tiles per sample (fc2's
+        forward and fc1's data gradient go to the library at stage 3; transposed = the node holds (w1^T, w2^T)), both weight gradients
+        run on the ring kernel with whole 64-row slabs per sample; then all six get the liveness;
+      * otherwise nothing skips in the forward pass and the backward products decide one by one, each with defined operands: the
+        GELU backward only if the two readers of d(pre) skip exactly, fc1's data gradient and the weight gradients wherever their kernel
+        takes the liveness (their dead rows of dy are exact zeros; a weight-gradient slab that straddles two samples is contracted)."""
+    B = M // rows_per_sample if rows_per_sample > 0 else 0
+    if not SAMPLE_SKIP or rows_per_sample <= 0 or M != B * rows_per_sample or not 0 < B <= 64:
+        return MlpSkip()
+    whole = lambda tile: tile > 0 and rows_per_sample % tile == 0
+    t_fc1 = gemm_nt_tile(M, C, hidden, "pswin_gemm_nt_gelu_fwd", required=True)
+    t_fc2 = gemm_nt_tile(M, hidden, C)
+    t_gelu = gemm_nt_tile(M, C, hidden, "pswin_gemm_nt_gelu_bwd", required=True) if transposed[1] else 0
+    t_dgrad = gemm_nt_tile(M, hidden, C) if transposed[0] else 0
+    s1, s2 = gemm_tn_ring_splits(M, hidden, C), gemm_tn_ring_splits(M, C, hidden)
+    dw1, dw2 = s1 > 0 and wgrad_live_rows_ok(M, s1), s2 > 0 and wgrad_live_rows_ok(M, s2)
+    slabs = rows_per_sample % 64 == 0
+    dgrad_exact = whole(t_dgrad) if need_dx else True
+    gelu_bwd = whole(t_gelu) and dgrad_exact and dw1 and slabs
+    fwd = whole(t_fc1) and whole(t_fc2) and gelu_bwd and dw2
+    return MlpSkip(fwd, gelu_bwd, whole(t_dgrad) and need_dx, dw1, dw2)
+
+
 class _MlpFused(torch.autograd.Function):
     """fc2(gelu(fc1(x) + b1)) WITHOUT fc2's bias for bf16 rows on the tiled GEMM (stages 1-3; HOT:44-61): fc1 with the bias + GELU
     in its epilogue (pswin_gemm_nt_gelu_fwd: the pre-activation is written once and never re-read in the forward pass), fc2;
     backward: fc2's data gradient with the GELU backward and the fc1 bias gradient in its epilogue (pswin_gemm_nt_gelu_bwd),
-    fc1's data gradient on the transposed weight copy, the two weight gradients as everywhere."""
+    fc1's data gradient on the transposed weight copy, the two weight gradients as everywhere.
+    sample_scale / rows_per_sample: the per-sample DropPath factors of the branch (None: none): the products named by mlp_sample_skip
+    leave out the rows of the samples whose factor is 0; their rows of the result and of dx are zeros."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, w1_lp, w1_lp_t, w2_lp, w2_lp_t):
+    def forward(ctx, x, w1, b1, w2, w1_lp, w1_lp_t, w2_lp, w2_lp_t, sample_scale=None, rows_per_sample=0):
         x = x.contiguous()
         M, K = x.shape
         w1b = w1_lp if w1_lp is not None else w1.to(x.dtype)
@@ -1176,23 +1267,35 @@ class _MlpFused(torch.autograd.Function):
         b = b1.detach().float().contiguous()
         pre = torch.empty(M, N, dtype=x.dtype, device=x.device)
         h = torch.empty_like(pre)
+        live = sample_liveness(sample_scale, rows_per_sample, M)
+        skip = MlpSkip()
+        if live is not None:
+            skip = mlp_sample_skip(M, K, N, rows_per_sample, (w1_lp_t is not None, w2_lp_t is not None), ctx.needs_input_grad[0])
         tile = gemm_nt_tile(M, K, N, "pswin_gemm_nt_gelu_fwd", required=True)
-        call("pswin_gemm_nt_gelu_fwd", x, ptr(x), ptr(w1b), ptr(b), ptr(pre), ptr(h), M, K, N, tile,
-             algo_bytes=2 * (M * K + 2 * M * N + N * K), algo_flops=2 * M * K * N)
-        out = linear_product(h, w2b)
+        if skip.fwd:
+            call("pswin_gemm_nt_gelu_fwd_live", x, ptr(x), ptr(w1b), ptr(b), ptr(pre), ptr(h), M, K, N, tile, ptr(live[0]), live[1],
+                 timed_as="pswin_gemm_nt_gelu_fwd", algo_bytes=2 * (M * K + 2 * M * N + N * K), algo_flops=2 * M * K * N)
+        else:
+            call("pswin_gemm_nt_gelu_fwd", x, ptr(x), ptr(w1b), ptr(b), ptr(pre), ptr(h), M, K, N, tile,
+                 algo_bytes=2 * (M * K + 2 * M * N + N * K), algo_flops=2 * M * K * N)
+        out = linear_product(h, w2b, live=live if skip.fwd else None)
         ctx.save_for_backward(x, pre, h, b, w1b, w1_lp_t, w2b, w2_lp_t)
         ctx.params = (w1, b1, w2)
+        ctx.live, ctx.skip = live, skip
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, pre, h, b, w1b, w1bt, w2b, w2bt = ctx.saved_tensors
         w1, b1, w2 = ctx.params
+        live, skip = ctx.live, ctx.skip
+        pick = lambda on: live if on else None
         dout = dout.contiguous()
-        dpre, db = gelu_data_gradient(dout, w2b, w2bt, pre, b, b1)     # fused: mlp_fused_supported checked the shape
-        _, dw2, _ = linear_backward(h, w2b, dout, w2, None, None, False)
-        dx, dw1, _ = linear_backward(x, w1b, dpre, w1, None, None, ctx.needs_input_grad[0], w1bt)
-        return dx, dw1, db, dw2, None, None, None, None
+        dpre, db = gelu_data_gradient(dout, w2b, w2bt, pre, b, b1, pick(skip.gelu_bwd))     # fused: mlp_fused_supported checked the shape
+        _, dw2, _ = linear_backward(h, w2b, dout, w2, None, None, False, wgrad_live=pick(skip.dw2))
+        dx, dw1, _ = linear_backward(x, w1b, dpre, w1, None, None, ctx.needs_input_grad[0], w1bt, wgrad_live=pick(skip.dw1),
+                                     dgrad_live=pick(skip.dgrad))
+        return dx, dw1, db, dw2, None, None, None, None, None, None
 
 
 def mlp_fused_supported(x2d, hidden):
@@ -1200,10 +1303,10 @@ def mlp_fused_supported(x2d, hidden):
             and bool(_lib.load().pswin_gemm_nt_supported(x2d.shape[0], x2d.shape[1], hidden)))
 
 
-def mlp_fused(x2d, fc1, fc2):
+def mlp_fused(x2d, fc1, fc2, sample_scale=None, rows_per_sample=0):
     """fc2_nobias(gelu(fc1(x2d))) as one autograd node on the tiled GEMM kernels: see _MlpFused."""
     (w1_lp, _, w1_lp_t), (w2_lp, _, w2_lp_t) = _lowp(fc1), _lowp(fc2)
-    return _MlpFused.apply(x2d, fc1.weight, fc1.bias, fc2.weight, w1_lp, w1_lp_t, w2_lp, w2_lp_t)
+    return _MlpFused.apply(x2d, fc1.weight, fc1.bias, fc2.weight, w1_lp, w1_lp_t, w2_lp, w2_lp_t, sample_scale, rows_per_sample)
 
 
 def bias_gelu_linear(y, bias1, lin2):
@@ -2163,11 +2266,12 @@ class _WindowAttentionQkvFused(torch.autograd.Function):
     to the unfused path."""
 
     @staticmethod
-    def forward(ctx, x, w_qkv, b_qkv, alpha, beta, dist, mask, heads, scale, n_bias_windows, wq_lp, wq_lp_t, grad_mode):
+    def forward(ctx, x, w_qkv, b_qkv, alpha, beta, dist, mask, heads, scale, n_bias_windows, wq_lp, wq_lp_t, grad_mode, live=None):
         x = x.contiguous()
         rows, C = x.shape
         n = rows // WTOK
         assert rows % WTOK == 0 and C == heads * _lib.HEAD_DIM
+        ctx.live = live                                     # sample liveness of the window rows: for the qkv weight gradient
         wq = (wq_lp if wq_lp is not None else w_qkv.to(x.dtype)).contiguous()
         bq = None if b_qkv is None else b_qkv.detach().float().contiguous()
         alpha_c = alpha.detach().contiguous() if dist is not None else None
@@ -2197,8 +2301,8 @@ class _WindowAttentionQkvFused(torch.autograd.Function):
         dqkv, _, _, dalpha, dbeta = attention_backward(qkv, None, None, lse, alpha_c, beta_c, dist, mask, datt, heads, scale, nb, None,
                                                         ctx.needs_input_grad[3] or ctx.needs_input_grad[4], (alpha, beta), packed=True)
         # the K third of d(qkv) sums to zero over every window (rows of dS sum to 0): its bias gradient is not summed
-        dx, dwq, dbq = linear_backward(x, wq, dqkv, w_qkv, b_qkv, (C, 2 * C), ctx.needs_input_grad[0], wq_t)
-        return dx, dwq, dbq, dalpha, dbeta, None, None, None, None, None, None, None, None
+        dx, dwq, dbq = linear_backward(x, wq, dqkv, w_qkv, b_qkv, (C, 2 * C), ctx.needs_input_grad[0], wq_t, wgrad_live=ctx.live)
+        return dx, dwq, dbq, dalpha, dbeta, None, None, None, None, None, None, None, None, None
 
 
 def window_attention_qkv_fused_supported(x2d, heads):
@@ -2207,10 +2311,10 @@ def window_attention_qkv_fused_supported(x2d, heads):
             and bool(_lib.load().pswin_qkv_attn_fused_supported(x2d.shape[1], heads, BF16)))
 
 
-def window_attention_qkv_fused(x2d, attn, dist, mask, n_bias_windows):
+def window_attention_qkv_fused(x2d, attn, dist, mask, n_bias_windows, live=None):
     """attention(qkv(x2d)) -- everything of WindowAttention.forward in front of self.proj -- for window rows x2d [n*49, C] and the
-    parameter holder `attn`: see _WindowAttentionQkvFused."""
+    parameter holder `attn`: see _WindowAttentionQkvFused.  live: the rows' sample liveness (sample_liveness) for the weight gradient."""
     wq_lp, _, wq_lp_t = _lowp(attn.qkv)
     return _WindowAttentionQkvFused.apply(x2d, attn.qkv.weight, attn.qkv.bias, attn.sphere_position_alpha_table_Te,
                                           attn.sphere_position_beta_table_Te, _as_tiles(dist), _as_tiles(mask), attn.num_heads, attn.scale,
-                                          n_bias_windows, wq_lp, wq_lp_t, torch.is_grad_enabled())
+                                          n_bias_windows, wq_lp, wq_lp_t, torch.is_grad_enabled(), live)
