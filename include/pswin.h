@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSWIN_ABI_VERSION 9
+#define PSWIN_ABI_VERSION 10
 
 #define PSWIN_F32 0
 #define PSWIN_BF16 1
@@ -853,6 +853,76 @@ int pswin_multiclass_nms_select(const float* top_keys, const long long* top_inde
 int pswin_paste_masks(const void* logits, int dtype, long long stride_n, long long stride_c, long long stride_y, long long stride_x,
                       const long long* labels, const float* boxes, const int32_t* count, int B, int K, int C, int H, int W, float thr,
                       unsigned char* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Test-time augmentation behind the heads (csrc/pswin_augtest.hip; panoswintransformerobjectdetection_amd/tta.py:
+ * map_to_view, map_back, merge_aug_proposals, merge_aug_bboxes, merge_aug_masks, aug_heads_predict)
+ * ---------------------------------------------------------------------------------------------- */
+
+#define PSWIN_AUG_VIEWS_MAX 8
+#define PSWIN_AUG_MASK_SOURCES_MAX 24
+
+/* The geometry of one test view, the same for every image of the batch: the unpadded size of the view's image, its scale factor
+ * (w, h, w, h) and whether it is flipped horizontally.  HOST data: an entry point copies the views into its launches. */
+typedef struct pswin_aug_view {
+    int img_h, img_w;
+    float scale[4];
+    int flip;
+} pswin_aug_view;
+
+/* The mask heads' outputs that one paste merges: `count` <= 24 tensors [B K][C][28][28] of one dtype on the device, each with its own
+ * element strides (NCHW or channels-last, as pswin_paste_masks takes them) and the flip flag of the view it was computed on.  HOST data. */
+typedef struct pswin_aug_mask_sources {
+    const void* logits[PSWIN_AUG_MASK_SOURCES_MAX];
+    long long stride_n[PSWIN_AUG_MASK_SOURCES_MAX], stride_c[PSWIN_AUG_MASK_SOURCES_MAX], stride_y[PSWIN_AUG_MASK_SOURCES_MAX],
+        stride_x[PSWIN_AUG_MASK_SOURCES_MAX];
+    int flip[PSWIN_AUG_MASK_SOURCES_MAX];
+    int count;
+} pswin_aug_mask_sources;
+
+/* merge_aug_proposals (mmdet/core/post_processing/merge_augs.py:12-80) for a batch: tta.merge_aug_proposals, bit for bit.
+ *   props f32 [V][B][P][4] and scores f32 [V][B][P]: the proposals of every view in the view's pixels; count int32 [V][B] on the DEVICE:
+ *   the first count[v][b] rows take part.  They are mapped back (un-flipped with the view's img_w, divided by its scale; float32,
+ *   operation by operation), concatenated view-major, visited in the order of (descending score, ascending concatenated position), a
+ *   candidate dropped when a kept one before it has IoU > iou_thr with it (the IoU of pswin_nms_groups), and the first
+ *   Pm = min(max_per_img, V P) survivors written to rois f32 [B][Pm][4], out_scores f32 [B][Pm], out_count int32 [B]; rows past the
+ *   count are zeros.  Three launches (pswin_aug_merge_proposals_launches), no atomics, nothing read back, every output row and every
+ *   workspace word that is read written by the call.  V <= 8, V P <= 8192, B <= 65535; workspace: pswin_aug_merge_proposals_workspace
+ *   bytes (the suppression masks: B * ceil64(V P)^2 / 8), 16-byte aligned.  NaN scores are outside the contract (the order is then
+ *   unspecified; nothing is read out of bounds). */
+int pswin_aug_merge_proposals_launches(int V, int P, int max_per_img);
+int pswin_aug_merge_proposals_workspace(int V, int B, int P, int max_per_img);
+int pswin_aug_merge_proposals(const float* props, const float* scores, const int32_t* count, const pswin_aug_view* views, int V, int B, int P,
+                              float iou_thr, int max_per_img, float* rois, float* out_scores, int32_t* out_count, void* workspace, void* stream);
+
+/* bbox_mapping (mmdet/core/bbox/transforms.py:34-43) of boxes f32 [B][N][4] into every view: out f32 [V][B][N][4] = box * scale, then
+ * x0' = img_w - x2, x2' = img_w - x0 where the view is flipped.  One launch; float32, operation by operation. */
+int pswin_aug_map_rois(const float* boxes, const pswin_aug_view* views, int V, int B, int N, float* out, void* stream);
+
+/* merge_aug_bboxes (merge_augs.py:83-109) behind the box heads of V views: rois / cls / deltas are HOST arrays of V device pointers to
+ * f32 [B][R][4], [B][R][C + 1] and [B][R][4 C] (cls and deltas f32 or bf16, read in place).  Per view softmax(cls) and
+ * detector.decode_deltas(rois, deltas, stds) clipped to the view's img_h x img_w and mapped back as above; over the views summed in view
+ * order and divided by V, in float32: boxes f32 [B][R][4 C], scores f32 [B][R][C + 1].  stds: HOST array of 4 floats.  One launch.
+ * R <= 1024, C <= 128. */
+int pswin_aug_merge_bboxes(const float* const* rois, const void* const* cls, const void* const* deltas, int cls_dtype, int deltas_dtype,
+                           const float* stds, const pswin_aug_view* views, int V, int B, int R, int C, float* boxes, float* scores, void* stream);
+
+/* The class-wise NMS chain above on GIVEN boxes and probabilities (merged_boxes f32 [B][R][4 C], scores f32 [B][R][C + 1]) instead of
+ * logits and deltas: the same three calls with the same two sorts of the caller between them, the same rule (strict > score_thr, ties by
+ * ascending r * C + c), the same outputs and limits; workspace: pswin_multiclass_nms_workspace(B, R, C). */
+int pswin_multiclass_nms_scores_boxes(const float* scores, const int32_t* roi_count, int B, int R, int C, float score_thr, float* keys,
+                                      void* stream);
+int pswin_multiclass_nms_boxes(const float* sorted_keys, const long long* sorted_index, const float* merged_boxes, int B, int R, int C,
+                               float iou_thr, float* final_keys, void* workspace, void* stream);
+int pswin_multiclass_nms_select_boxes(const float* top_keys, const long long* top_index, long long row_stride, int n_sorted,
+                                      const float* merged_boxes, int B, int R, int C, int K, float* boxes, float* scores, long long* labels,
+                                      int32_t* source, int32_t* count, void* stream);
+
+/* pswin_paste_masks whose pasted 28 x 28 probability is merge_aug_masks (merge_augs.py:120-150) of the sources: the mean, in source order
+ * and float32, of sigmoid(logits_s[b K + k][labels[b][k]]) with the column index reversed where flip[s].  The mean lives in LDS only.
+ * Everything else as pswin_paste_masks. */
+int pswin_paste_masks_aug(const pswin_aug_mask_sources* sources, int dtype, const long long* labels, const float* boxes, const int32_t* count,
+                          int B, int K, int C, int H, int W, float thr, unsigned char* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Detector training between "assigned" and "loss" for a padded batch (csrc/pswin_targets.hip;

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PSWIN_LIB") or os.path.join(_PKG, "libpswin_hip.so") 
 F32, BF16 = 0, 1
 MODE_PLANAR, MODE_PANO = 0, 1
 WS, WTOK, WPAD, HEAD_DIM = 7, 49, 64, 32
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -90,6 +90,15 @@ _PROTOTYPES = {
     "pswin_multiclass_nms_select": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pswin_paste_masks": [_vp, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                           _f, _vp, _vp],
+    "pswin_aug_merge_proposals_launches": [_i, _i, _i],
+    "pswin_aug_merge_proposals_workspace": [_i, _i, _i, _i],
+    "pswin_aug_merge_proposals": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
+    "pswin_aug_map_rois": [_vp, _vp, _i, _i, _i, _vp, _vp],
+    "pswin_aug_merge_bboxes": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "pswin_multiclass_nms_scores_boxes": [_vp, _vp, _i, _i, _i, _f, _vp, _vp],
+    "pswin_multiclass_nms_boxes": [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
+    "pswin_multiclass_nms_select_boxes": [_vp, _vp, ctypes.c_longlong, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pswin_paste_masks_aug": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp],
     "pswin_sample_rows_per_workgroup": [],
     "pswin_sample_workspace": [_i, _i, _i],
     "pswin_sample_ranks": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
@@ -220,6 +229,17 @@ class RoiLevels(ctypes.Structure):
     """pswin_roi_levels of include/pswin.h"""
     _fields_ = [("feat", ctypes.c_void_p * 4), ("dfeat", ctypes.c_void_p * 4), ("H", ctypes.c_int * 4), ("W", ctypes.c_int * 4),
                 ("spatial_scale", ctypes.c_float * 4), ("n_levels", ctypes.c_int)]
+
+
+class AugView(ctypes.Structure):
+    """pswin_aug_view of include/pswin.h"""
+    _fields_ = [("img_h", ctypes.c_int), ("img_w", ctypes.c_int), ("scale", ctypes.c_float * 4), ("flip", ctypes.c_int)]
+
+
+class AugMaskSources(ctypes.Structure):
+    """pswin_aug_mask_sources of include/pswin.h"""
+    _fields_ = [("logits", ctypes.c_void_p * 24), ("stride_n", ctypes.c_longlong * 24), ("stride_c", ctypes.c_longlong * 24),
+                ("stride_y", ctypes.c_longlong * 24), ("stride_x", ctypes.c_longlong * 24), ("flip", ctypes.c_int * 24), ("count", ctypes.c_int)]
 
 
 class TableGradJob(ctypes.Structure):

@@ -195,7 +195,8 @@ class MiniCascadeRCNN(det.MiniMaskRCNN):
         marked ignored after the assignment (stage_sample): no sampler can draw them, and the shapes stay fixed.
       * The next stage of the reference samples from (its gt boxes + the up to 512 kept RoIs) and draws fewer than 512 when they do not hold
         enough negatives.  With fixed shapes every stage fills its 512 slots as detector.roi_targets does: negatives first.
-      * Class-agnostic regression, aug_test and the joint gradient clipping of the heads are not part of it."""
+      * Class-agnostic regression and the joint gradient clipping of the heads are not part of it.  aug_test is tta.aug_heads_predict
+        through view_box_outputs / view_mask_logits below."""
 
     refine = staticmethod(refine_rois_dispatch)                   # a stage's class choice, regression and clip, once per batch
     giou_rows = staticmethod(giou_rows_dispatch)                  # the box loss on decoded boxes, row by row
@@ -373,3 +374,30 @@ class MiniCascadeRCNN(det.MiniMaskRCNN):
         if return_raw:
             return out, dict(rois=rois_s, roi_count=roi_count, cls=cls_s, deltas=reg_s, mask_logits=mask_logits)
         return out
+
+    # -- test-time augmentation (tta.py) ----------------------------------------------------------------------------------
+    @torch.no_grad()
+    def view_box_outputs(self, fpn, rois, img_hw, dtype=None):
+        """The box outputs of ONE test view given its RoIs (CascadeRoIHead.aug_test's loop body, cascade_roi_head.py:424-455): the three
+        stages run in the view, `refine` clips to the view's img_hw -> (the last stage's RoIs [B, R, 4], ensemble_logits of the three
+        stages [B, R, C + 1], the last stage's deltas [B, R, 4 C], the last stage's stds)."""
+        B, R, C = rois.shape[0], rois.shape[1], self.num_classes
+        auto = dict(device_type="cuda", dtype=torch.bfloat16, enabled=rois.is_cuda)
+        rois_s, cls_s, reg = [rois], [], None
+        for i in range(self.NUM_STAGES):
+            with torch.autocast(**auto):
+                x = self.roi_align(fpn[:4], self.STRIDES[:4], rois_s[i], 7)
+                cls, reg = self.bbox_heads[i](x.to(dtype or fpn[0].dtype))
+            cls_s.append(cls.view(B, R, C + 1))
+            reg = reg.view(B, R, 4 * C)
+            if i + 1 < self.NUM_STAGES:
+                rois_s.append(self.refine(rois_s[i], cls_s[i], reg, None, self.rcnn_cfg[i]["stds"], img_hw)[0])
+        return rois_s[-1], ensemble_logits(cls_s), reg, self.rcnn_cfg[-1]["stds"]
+
+    @torch.no_grad()
+    def view_mask_logits(self, fpn, rois, dtype=None):
+        """The mask logits of ONE test view given its RoIs (cascade_roi_head.py:476-490): a list of three [B K, C, 28, 28], one per stage's
+        mask head -- merge_aug_masks takes all V x 3 as sources."""
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=rois.is_cuda):
+            xm = self.roi_align(fpn[:4], self.STRIDES[:4], rois, 14).to(dtype or fpn[0].dtype)
+            return [h(xm) for h in self.mask_heads]

@@ -20,20 +20,10 @@
 //   grid_sample's zero padding without a bounds test), then samples it bilinearly for PASTE_ROWS image rows with grid_sample's
 //   align_corners=False geometry and stores (value >= thr) as bytes, 16 pixels per lane and store where the row's address allows.
 //   Neither the float image nor the sampling grid exists in memory; rows of detections past the image's count are written as zeros.
-#include "pswin_common.hpp"
+#include "pswin_detect_post.hpp"
 
 namespace {
 using namespace pswin;
-
-constexpr int DET_RMAX = 1024, DET_CMAX = 128, DET_KMAX = 1024, DET_THREADS = 256;
-constexpr int DET_NMS_SLICE = 256;                      // (image, class) groups per pswin_nms_groups call: 64 MiB of masks at 1024 rows
-constexpr int PASTE_M = 28, PASTE_LD = PASTE_M + 2, PASTE_THREADS = 256, PASTE_ROWS = 32;
-
-__device__ inline float det_load(const void* p, int dt, size_t i) {
-    return dt == PSWIN_F32 ? reinterpret_cast<const float*>(p)[i] : bf16_bits_to_f32(reinterpret_cast<const unsigned short*>(p)[i]);
-}
-
-__device__ inline int det_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 struct DetDecode {
     float std[4];
@@ -42,6 +32,7 @@ struct DetDecode {
     const float* rois;                                  // f32 [B][R][4]
     const void* deltas;                                 // [B][R][4 C]
     int deltas_dt, R, C;
+    __device__ inline f32x4 operator()(int b, int r, int c) const;   // det_box: what the chain's kernels call (pswin_detect_post.hpp)
 };
 
 // detector.decode_deltas for class c of proposal r of image b (means 0, the width / height deltas clamped at |log(16 / 1000)|, the box
@@ -70,6 +61,8 @@ __device__ inline f32x4 det_box(const DetDecode& p, int b, int r, int c) {
     return f32x4{(float)x1, (float)y1, (float)x2, (float)y2};
 }
 
+__device__ inline f32x4 DetDecode::operator()(int b, int r, int c) const { return det_box(*this, b, r, c); }
+
 // (1) one thread per proposal: key[b][c][r] = softmax(logits[b][r])[c] if it is above the threshold and r < roi_count[b], else -1
 __global__ __launch_bounds__(DET_THREADS) void det_scores_kernel(const void* __restrict__ cls, int cls_dt, const int* __restrict__ roi_count, int R,
                                                                  int C, float score_thr, float* __restrict__ keys) {
@@ -92,90 +85,6 @@ __global__ __launch_bounds__(DET_THREADS) void det_scores_kernel(const void* __r
     }
 }
 
-// (2a) one thread per (image, class, sorted position): the candidate's box into the NMS input, and the list's candidate count (written by
-// the one thread that sees the last candidate, or by thread 0 of a list without any)
-__global__ __launch_bounds__(DET_THREADS) void det_gather_kernel(const float* __restrict__ skeys, const long long* __restrict__ sidx, DetDecode p,
-                                                                 int Rp, float* __restrict__ sboxes, int* __restrict__ counts) {
-    const int b = blockIdx.z, c = blockIdx.y, j = blockIdx.x * DET_THREADS + threadIdx.x;
-    if (j >= p.R) return;
-    const size_t g = (size_t)b * p.C + c;
-    const bool valid = skeys[g * p.R + j] > 0.f;
-    if (valid) {
-        const int r = det_clamp((int)sidx[g * p.R + j], p.R - 1);
-        reinterpret_cast<f32x4*>(sboxes)[g * Rp + j] = det_box(p, b, r, c);
-        if (j + 1 >= p.R || !(skeys[g * p.R + j + 1] > 0.f)) counts[g] = j + 1;
-    } else if (j == 0) {
-        counts[g] = 0;
-    }
-}
-
-// (2b) final[b][r * C + c] = the score of a candidate the NMS kept, else -1
-__global__ __launch_bounds__(DET_THREADS) void det_scatter_kernel(const float* __restrict__ skeys, const long long* __restrict__ sidx,
-                                                                  const unsigned char* __restrict__ keep, int R, int Rp, int C,
-                                                                  float* __restrict__ final_keys) {
-    const int b = blockIdx.z, c = blockIdx.y, j = blockIdx.x * DET_THREADS + threadIdx.x;
-    if (j >= R) return;
-    const size_t g = (size_t)b * C + c;
-    const float key = skeys[g * R + j];
-    const int r = det_clamp((int)sidx[g * R + j], R - 1);
-    const bool kept = key > 0.f && keep[g * Rp + j] != 0;
-    final_keys[((size_t)b * R + r) * C + c] = kept ? key : -1.f;
-}
-
-// (3) one thread per (image, output row)
-__global__ __launch_bounds__(DET_THREADS) void det_select_kernel(const float* __restrict__ tvals, const long long* __restrict__ tidx, long long ld,
-                                                                 int n_sorted, DetDecode p, int K, float* __restrict__ boxes,
-                                                                 float* __restrict__ scores, long long* __restrict__ labels,
-                                                                 int* __restrict__ source, int* __restrict__ count) {
-    const int b = blockIdx.y, k = blockIdx.x * DET_THREADS + threadIdx.x;
-    if (k >= K) return;
-    const size_t row = (size_t)b * (size_t)ld;
-    const float v = k < n_sorted ? tvals[row + k] : -1.f;
-    const size_t o = (size_t)b * K + k;
-    f32x4 box = {0.f, 0.f, 0.f, 0.f};
-    float sc = 0.f;
-    long long lab = 0;
-    int src = 0;
-    if (v > 0.f) {
-        long long flat = tidx[row + k];
-        const long long last = (long long)p.R * p.C - 1;
-        flat = flat < 0 ? 0 : (flat > last ? last : flat);
-        const int r = (int)(flat / p.C), c = (int)(flat % p.C);
-        box = det_box(p, b, r, c);
-        sc = v;
-        lab = c;
-        src = (int)flat;
-        const bool more = k + 1 < K && k + 1 < n_sorted && tvals[row + k + 1] > 0.f;
-        if (!more) count[b] = k + 1;
-    } else if (k == 0) {
-        count[b] = 0;
-    }
-    reinterpret_cast<f32x4*>(boxes)[o] = box;
-    scores[o] = sc;
-    labels[o] = lab;
-    source[o] = src;
-}
-
-bool det_shape_ok(int B, int R, int C) { return B >= 1 && B <= 65535 && R >= 1 && R <= DET_RMAX && C >= 1 && C <= DET_CMAX; }
-
-struct DetWorkspace {
-    size_t boxes, counts, keep, masks, total;
-    int Rp, slice;
-};
-
-DetWorkspace det_workspace(int B, int R, int C) {
-    DetWorkspace w;
-    const size_t G = (size_t)B * C;
-    w.Rp = ceil_to(R, 64);
-    w.slice = G < (size_t)DET_NMS_SLICE ? (int)G : DET_NMS_SLICE;
-    w.boxes = 0;
-    w.counts = w.boxes + G * w.Rp * 16;
-    w.keep = w.counts + (G * 4 + 15) / 16 * 16;
-    w.masks = w.keep + (G * w.Rp + 15) / 16 * 16;
-    w.total = w.masks + (size_t)w.slice * w.Rp * 32 * 8;   // pswin_nms_workspace(slice, Rp)
-    return w;
-}
-
 DetDecode det_decode_args(const float* rois, const void* deltas, int deltas_dtype, const float* stds, int img_h, int img_w, const float* scale, int R,
                           int C) {
     DetDecode p;
@@ -191,16 +100,7 @@ DetDecode det_decode_args(const float* rois, const void* deltas, int deltas_dtyp
     return p;
 }
 
-// ---- mask paste ----------------------------------------------------------------------------------------------------------------------------
-// grid_sample's source coordinate of an image pixel centre `pc` (x + 0.5 or y + 0.5) for a box side [lo, hi]: the normalised coordinate
-// (pc - lo) / (hi - lo) * 2 - 1 with an infinite value set to 0 (_do_paste_mask), then ((g + 1) * 28 - 1) / 2 (align_corners=False).
-// A NaN (0 / 0: the centre lies on a box side of zero length) comes back as NaN: the pixel samples nothing.
-__device__ inline float paste_coord(float pc, float lo, float hi) {
-    float g = (pc - lo) / (hi - lo) * 2.f - 1.f;
-    if (__builtin_isinf(g)) g = 0.f;
-    return ((g + 1.f) * (float)PASTE_M - 1.f) / 2.f;
-}
-
+// ---- mask paste: the staging of one source; the sampling and the stores are paste_rows (pswin_detect_post.hpp) --------------------------------
 template <int DT>
 __global__ __launch_bounds__(PASTE_THREADS) void paste_kernel(const void* __restrict__ logits, long long sn, long long sc, long long sy,
                                                               long long sx, const long long* __restrict__ labels, const float* __restrict__ boxes,
@@ -225,66 +125,7 @@ __global__ __launch_bounds__(PASTE_THREADS) void paste_kernel(const void* __rest
             prob[i] = v;
         }
     }
-    __syncthreads();
-    const unsigned zero_bit = 0.f >= thr ? 1u : 0u;     // what a pixel that samples nothing compares to
-    const bool whole = (W & 15) == 0;                   // every row starts on a 16-byte boundary: vector stores only
-    const int SL = whole ? W >> 4 : (W >> 4) + 2;       // work items per row: the 16-pixel groups, then the row's unaligned head and tail
-    const int rows = H - ybase < PASTE_ROWS ? H - ybase : PASTE_ROWS;
-    for (int it = t; it < rows * SL; it += PASTE_THREADS) {
-        const int y = ybase + it / SL, s = it % SL;
-        const size_t rowoff = (det * H + y) * (size_t)W;
-        int head = whole ? 0 : (int)((16 - (rowoff & 15)) & 15);
-        head = head > W ? W : head;
-        const int nvec = (W - head) >> 4;
-        int xs, n;
-        if (s < nvec) {
-            xs = head + 16 * s;
-            n = 16;
-        } else if (s == nvec) {
-            xs = 0;
-            n = head;
-        } else if (s == nvec + 1) {
-            xs = head + 16 * nvec;
-            n = W - xs;
-        } else {
-            continue;
-        }
-        unsigned bits = 0u;                             // bit p: pixel xs + p
-        if (live) {
-            const float iy = paste_coord((float)y + 0.5f, box[1], box[3]);
-            if (iy > -1.f && iy < (float)PASTE_M) {
-                const float yf = floorf(iy);
-                const float wy1 = iy - yf, wy0 = (yf + 1.f) - iy;
-                const float* pr = prob + ((int)yf + 1) * PASTE_LD + 1;
-#pragma unroll
-                for (int p = 0; p < 16; ++p) {
-                    const float ix = paste_coord((float)(xs + p) + 0.5f, box[0], box[2]);
-                    float val = 0.f;
-                    if (ix > -1.f && ix < (float)PASTE_M) {
-                        const float xf = floorf(ix);
-                        const float wx1 = ix - xf, wx0 = (xf + 1.f) - ix;
-                        const float* q = pr + (int)xf;
-                        val = q[0] * (wx0 * wy0) + q[1] * (wx1 * wy0) + q[PASTE_LD] * (wx0 * wy1) + q[PASTE_LD + 1] * (wx1 * wy1);
-                    }
-                    bits |= (val >= thr ? 1u : 0u) << p;
-                }
-            } else {
-                bits = zero_bit ? 0xffffu : 0u;
-            }
-        }
-        unsigned char* dst = out + rowoff + xs;
-        if (n == 16) {
-            u32x4 v;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const unsigned nib = (bits >> (4 * q)) & 15u;
-                v[q] = (nib & 1u) | ((nib & 2u) << 7) | ((nib & 4u) << 14) | ((nib & 8u) << 21);
-            }
-            *reinterpret_cast<u32x4*>(dst) = v;         // xs + 16 <= W and (rowoff + xs) % 16 == 0
-        } else {
-            for (int p = 0; p < n; ++p) dst[p] = (unsigned char)((bits >> p) & 1u);
-        }
-    }
+    paste_rows(prob, live, box, det, ybase, H, W, thr, out);
 }
 
 }  // namespace
@@ -314,23 +155,8 @@ int pswin_multiclass_nms(const float* sorted_keys, const long long* sorted_index
     PSWIN_CHECK_ARG(aligned16(rois) && aligned16(workspace) && (!scale || aligned16(scale)) && (reinterpret_cast<uintptr_t>(sorted_index) & 7) == 0);
     PSWIN_CHECK_ARG((reinterpret_cast<uintptr_t>(deltas) & 7) == 0 && (reinterpret_cast<uintptr_t>(sorted_keys) & 3) == 0 &&
                     (reinterpret_cast<uintptr_t>(final_keys) & 3) == 0);
-    const DetWorkspace w = det_workspace(B, R, C);
-    PSWIN_CHECK_ARG(w.total <= 0x7fffffffull);
-    char* ws = reinterpret_cast<char*>(workspace);
-    float* sboxes = reinterpret_cast<float*>(ws + w.boxes);
-    int* counts = reinterpret_cast<int*>(ws + w.counts);
-    unsigned char* keep = reinterpret_cast<unsigned char*>(ws + w.keep);
-    const DetDecode p = det_decode_args(rois, deltas, deltas_dtype, stds, img_h, img_w, scale, R, C);
-    const dim3 grid((R + DET_THREADS - 1) / DET_THREADS, C, B);
-    hipLaunchKernelGGL(det_gather_kernel, grid, dim3(DET_THREADS), 0, (hipStream_t)stream, sorted_keys, sorted_index, p, w.Rp, sboxes, counts);
-    const int G = B * C;
-    for (int g0 = 0; g0 < G; g0 += w.slice) {           // the slices run one after the other on the stream and share the mask words
-        const int n = G - g0 < w.slice ? G - g0 : w.slice;
-        const int rc = pswin_nms_groups(sboxes + (size_t)g0 * w.Rp * 4, counts + g0, n, w.Rp, iou_thr, keep + (size_t)g0 * w.Rp, ws + w.masks, stream);
-        if (rc != PSWIN_OK) return rc;
-    }
-    hipLaunchKernelGGL(det_scatter_kernel, grid, dim3(DET_THREADS), 0, (hipStream_t)stream, sorted_keys, sorted_index, keep, R, w.Rp, C, final_keys);
-    PSWIN_LAUNCH_RET();
+    return det_nms_lists(sorted_keys, sorted_index, det_decode_args(rois, deltas, deltas_dtype, stds, img_h, img_w, scale, R, C), B, iou_thr,
+                         final_keys, workspace, stream);
 }
 
 int pswin_multiclass_nms_select(const float* top_keys, const long long* top_index, long long row_stride, int n_sorted, const float* rois,
@@ -343,10 +169,8 @@ int pswin_multiclass_nms_select(const float* top_keys, const long long* top_inde
     PSWIN_CHECK_ARG((reinterpret_cast<uintptr_t>(top_index) & 7) == 0 && (reinterpret_cast<uintptr_t>(labels) & 7) == 0 &&
                     (reinterpret_cast<uintptr_t>(top_keys) & 3) == 0 && (reinterpret_cast<uintptr_t>(scores) & 3) == 0 &&
                     (reinterpret_cast<uintptr_t>(source) & 3) == 0 && (reinterpret_cast<uintptr_t>(count) & 3) == 0);
-    const DetDecode p = det_decode_args(rois, deltas, deltas_dtype, stds, img_h, img_w, scale, R, C);
-    hipLaunchKernelGGL(det_select_kernel, dim3((K + DET_THREADS - 1) / DET_THREADS, B), dim3(DET_THREADS), 0, (hipStream_t)stream, top_keys, top_index,
-                       row_stride, n_sorted, p, K, boxes, scores, labels, source, count);
-    PSWIN_LAUNCH_RET();
+    return det_select(top_keys, top_index, row_stride, n_sorted, det_decode_args(rois, deltas, deltas_dtype, stds, img_h, img_w, scale, R, C), B, K,
+                      boxes, scores, labels, source, count, stream);
 }
 
 int pswin_paste_masks(const void* logits, int dtype, long long stride_n, long long stride_c, long long stride_y, long long stride_x,

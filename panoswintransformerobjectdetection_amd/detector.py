@@ -891,6 +891,37 @@ class MiniMaskRCNN(nn.Module):
         """backbone + heads_predict (TwoStageDetector.simple_test): a Detections for the batch"""
         return self.heads_predict(self.backbone(img), img.shape[2:], **kw)
 
+    # -- test-time augmentation (tta.py) ----------------------------------------------------------------------------------
+    @torch.no_grad()
+    def view_box_outputs(self, fpn, rois, img_hw, dtype=None):
+        """The box outputs of ONE test view given its RoIs (aug_test_bboxes' loop body, test_mixins.py:170-188): fpn = the view's pyramid,
+        rois f32 [B, R, 4] in the view's pixels -> (rois [B, R, 4], cls [B, R, C + 1], deltas [B, R, 4 C], stds), what the decoder takes.
+        dtype: what the RoI features are cast to (default: the pyramid's)."""
+        B, R, C = rois.shape[0], rois.shape[1], self.num_classes
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=rois.is_cuda):
+            x = self.roi_align(fpn[:4], self.STRIDES[:4], rois, 7)
+            cls, reg = self.bbox_head(x.to(dtype or fpn[0].dtype))
+        return rois, cls.view(B, R, C + 1), reg.view(B, R, 4 * C), self.BBOX_STDS
+
+    @torch.no_grad()
+    def view_mask_logits(self, fpn, rois, dtype=None):
+        """The mask logits of ONE test view given its RoIs (aug_test_mask's loop body, test_mixins.py:325-336): rois f32 [B, K, 4] in the
+        view's pixels -> a list of [B K, C, 28, 28], one per mask head."""
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=rois.is_cuda):
+            xm = self.roi_align(fpn[:4], self.STRIDES[:4], rois, 14)
+            return [self.mask_head(xm.to(dtype or fpn[0].dtype))]
+
+    def aug_heads_predict(self, feats_list, views, **kw):
+        """tta.aug_heads_predict: everything behind the backbone of aug_test -- a Detections at the original image scale"""
+        from . import tta
+        return tta.aug_heads_predict(self, feats_list, views, **kw)
+
+    def aug_test(self, imgs_list, views, **kw):
+        """backbone per view + aug_heads_predict (TwoStageDetector.aug_test, two_stage.py:236-245): imgs_list = one image batch per view
+        (pano_aug.test_views builds them), views = their tta.View"""
+        from . import tta
+        return tta.aug_test(self, imgs_list, views, **kw)
+
 
 def synthetic_targets(batch, H, W, device, num_classes=80, seed=0):
     """COCO-shaped synthetic targets as the reference's own detector tests build them (tests/test_models/test_forward.py:

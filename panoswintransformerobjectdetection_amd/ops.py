@@ -1943,6 +1943,208 @@ def paste_masks(mask_logits, labels, boxes, count, thr, out_hw, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# test-time augmentation: the merges of tta.py on the GPU (csrc/pswin_augtest.hip)
+# ------------------------------------------------------------------------------------------------
+def _aug_views(views):
+    """tta.View list -> (the host array of pswin_aug_view, its pointer); V <= 8"""
+    if not 1 <= len(views) <= 8:
+        raise PswinError(f"test-time augmentation takes 1 to 8 views, got {len(views)}")
+    arr = (_lib.AugView * len(views))()
+    for a, v in zip(arr, views):
+        a.img_h, a.img_w, a.flip = int(v.img_hw[0]), int(v.img_hw[1]), int(bool(v.flip))
+        a.scale[:] = [float(s) for s in v.scale_factor]
+    return arr, ctypes.cast(arr, ctypes.c_void_p)
+
+
+def _aug_out(out, what, dev, *specs):
+    """the output buffers of a call: new ones, or the caller's `out` tuple checked against (shape, dtype) specs"""
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dt, device=dev) for shape, dt in specs)
+    out = tuple(out) if isinstance(out, (tuple, list)) else (out,)
+    if len(out) != len(specs) or any(o.dtype != dt or tuple(o.shape) != tuple(shape) or o.device != dev or not o.is_contiguous()
+                                     for o, (shape, dt) in zip(out, specs)):
+        raise PswinError(f"{what}: out must be contiguous tensors of {[(tuple(sh), dt) for sh, dt in specs]} on the inputs' device")
+    return out
+
+
+def aug_merge_proposals_supported(V, B, P, max_per_img):
+    """Whether pswin_aug_merge_proposals takes the shape: V <= 8, V P <= 8192 and a workspace below 2^31 bytes"""
+    return int(_lib.load().pswin_aug_merge_proposals_workspace(int(V), int(B), int(P), int(max_per_img))) > 0
+
+
+def aug_merge_proposals_launches(V, P, max_per_img):
+    """The kernel launches of one pswin_aug_merge_proposals call, whatever the batch"""
+    n = int(_lib.load().pswin_aug_merge_proposals_launches(int(V), int(P), int(max_per_img)))
+    _lib.check(min(n, 0), "pswin_aug_merge_proposals_launches")
+    return n
+
+
+def aug_merge_proposals(props, scores, count, views, iou_thr, max_per_img, out=None):
+    """tta.merge_aug_proposals on the GPU, bit for bit (pswin_aug_merge_proposals: three launches): props f32 [V, B, P, 4], scores f32
+    [V, B, P], count int32 [V, B] ON THE DEVICE -> (rois f32 [B, Pm, 4], scores f32 [B, Pm], count int32 [B]), Pm = min(max_per_img, V P).
+    V <= 8, V P <= 8192; beyond: PswinError.  No atomics, no host synchronisation; the workspace is cached per shape and every part of it
+    that a call reads the call has written.  out: (rois, scores, count) buffers to write instead of new ones (every element is written).
+    CPU tensors: the definition."""
+    if not props.is_cuda:
+        from . import tta
+        return tta.merge_aug_proposals(props, scores, count, views, iou_thr, max_per_img)
+    if props.dim() != 4 or props.shape[3] != 4 or tuple(scores.shape) != tuple(props.shape[:3]) or tuple(count.shape) != tuple(props.shape[:2]) or \
+            len(views) != props.shape[0]:
+        raise PswinError(f"aug_merge_proposals: props [V, B, P, 4], scores [V, B, P], count [V, B] and V views, got {tuple(props.shape)}, "
+                         f"{tuple(scores.shape)}, {tuple(count.shape)} and {len(views)}")
+    V, B, P = (int(v) for v in props.shape[:3])
+    dev = props.device
+    if count.dtype != torch.int32 or count.device != dev or scores.device != dev:
+        raise PswinError("aug_merge_proposals: count must be an int32 tensor on the device of the proposals")
+    max_per_img = int(max_per_img)
+    if not aug_merge_proposals_supported(V, B, P, max_per_img):
+        raise PswinError(f"aug_merge_proposals: outside the kernels' limits (V <= 8, V P <= 8192): V = {V}, B = {B}, P = {P}")
+    props, scores, count = props.detach().float().contiguous(), scores.detach().float().contiguous(), count.contiguous()
+    key = ("aug_proposals_ws", V, B, P, max_per_img, _dev_key(dev))
+    if key not in _CACHE:
+        _CACHE[key] = torch.empty(int(_lib.load().pswin_aug_merge_proposals_workspace(V, B, P, max_per_img)), dtype=torch.uint8, device=dev)
+    Pm = min(max_per_img, V * P)
+    rois, out_scores, out_count = _aug_out(out, "aug_merge_proposals", dev, ((B, Pm, 4), torch.float32), ((B, Pm), torch.float32), ((B,), torch.int32))
+    arr, vp = _aug_views(views)
+    call("pswin_aug_merge_proposals", props, ptr(props), ptr(scores), ptr(count), vp, V, B, P, ctypes.c_float(float(iou_thr)), max_per_img,
+         ptr(rois), ptr(out_scores), ptr(out_count), ptr(_CACHE[key]))
+    return rois, out_scores, out_count
+
+
+def aug_map_rois(boxes, views, out=None):
+    """tta.map_to_view of boxes f32 [B, N, 4] into every view, bit for bit, in one launch (pswin_aug_map_rois): f32 [V, B, N, 4].
+    CPU tensors: the definition."""
+    if not boxes.is_cuda:
+        from . import tta
+        return torch.stack([tta.map_to_view(boxes, v) for v in views])
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise PswinError(f"aug_map_rois: boxes [B, N, 4], got {tuple(boxes.shape)}")
+    boxes = boxes.detach().float().contiguous()
+    B, N = int(boxes.shape[0]), int(boxes.shape[1])
+    out, = _aug_out(out, "aug_map_rois", boxes.device, ((len(views), B, N, 4), torch.float32))
+    arr, vp = _aug_views(views)
+    call("pswin_aug_map_rois", boxes, ptr(boxes), vp, len(views), B, N, ptr(out))
+    return out
+
+
+def aug_merge_bboxes(rois_v, cls_v, deltas_v, stds, views, out=None):
+    """tta.merge_aug_bboxes on the GPU in one launch (pswin_aug_merge_bboxes): rois_v / cls_v / deltas_v are sequences of V tensors
+    [B, R, 4] / [B, R, C + 1] / [B, R, 4 C] (or one stacked tensor each); cls and deltas f32 or bf16 of one dtype each, read in place ->
+    (boxes f32 [B, R, 4 C], scores f32 [B, R, C + 1]).  R <= 1024, C <= 128, V <= 8.  CPU tensors: the definition."""
+    rois_v, cls_v, deltas_v = list(rois_v), list(cls_v), list(deltas_v)
+    if not cls_v[0].is_cuda:
+        from . import tta
+        return tta.merge_aug_bboxes(rois_v, cls_v, deltas_v, stds, views)
+    V = len(views)
+    if not (len(rois_v) == len(cls_v) == len(deltas_v) == V):
+        raise PswinError(f"aug_merge_bboxes: one rois, cls and deltas tensor per view, got {len(rois_v)}, {len(cls_v)}, {len(deltas_v)} for {V} views")
+    B, R, C = int(cls_v[0].shape[0]), int(cls_v[0].shape[1]), int(cls_v[0].shape[2]) - 1
+    dev = cls_v[0].device
+    rois_v = [r.detach().float().contiguous() for r in rois_v]
+    cdt = cls_v[0].dtype if cls_v[0].dtype in (torch.float32, torch.bfloat16) else torch.float32
+    ddt = deltas_v[0].dtype if deltas_v[0].dtype in (torch.float32, torch.bfloat16) else torch.float32
+    cls_v = [c.detach().to(cdt).contiguous() for c in cls_v]
+    deltas_v = [d.detach().to(ddt).contiguous() for d in deltas_v]
+    for r, c, d in zip(rois_v, cls_v, deltas_v):
+        if tuple(r.shape) != (B, R, 4) or tuple(c.shape) != (B, R, C + 1) or tuple(d.shape) != (B, R, 4 * C) or r.device != dev or d.device != dev:
+            raise PswinError(f"aug_merge_bboxes: every view takes rois [B, R, 4], cls [B, R, C + 1], deltas [B, R, 4 C] on one device, got "
+                             f"{tuple(r.shape)}, {tuple(c.shape)}, {tuple(d.shape)}")
+
+    def ptrs(ts):
+        a = (ctypes.c_void_p * V)(*[t.data_ptr() for t in ts])
+        return a, ctypes.cast(a, ctypes.c_void_p)
+    (ra, rp), (ca, cp), (da, dp) = ptrs(rois_v), ptrs(cls_v), ptrs(deltas_v)
+    std4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    boxes, scores = _aug_out(out, "aug_merge_bboxes", dev, ((B, R, 4 * C), torch.float32), ((B, R, C + 1), torch.float32))
+    arr, vp = _aug_views(views)
+    call("pswin_aug_merge_bboxes", boxes, rp, cp, dp, dtype_code(cls_v[0]), dtype_code(deltas_v[0]), ctypes.cast(std4, ctypes.c_void_p), vp, V, B,
+         R, C, ptr(boxes), ptr(scores))
+    return boxes, scores
+
+
+def multiclass_nms_boxes_batch(merged_boxes, merged_scores, roi_count, score_thr, iou_thr, K, out=None):
+    """detector.multiclass_nms for every image of a batch on GIVEN boxes and probabilities (pswin_multiclass_nms_scores_boxes -> sort ->
+    pswin_multiclass_nms_boxes -> sort -> pswin_multiclass_nms_select_boxes), the chain of multiclass_nms_batch behind its softmax and
+    decode: merged_boxes f32 [B, R, 4 C], merged_scores f32 [B, R, C + 1], roi_count int32 [B] ON THE DEVICE (the first roi_count[b] rows
+    of image b take part) -> (boxes f32 [B, K, 4], scores f32 [B, K], labels int64 [B, K], count int32 [B], source int32 [B, K]).
+    Capturable as multiclass_nms_batch is.  CPU tensors: the definition (tta.nms_merged)."""
+    if not merged_boxes.is_cuda:
+        from . import tta
+        return tta.nms_merged(merged_boxes, merged_scores, roi_count, score_thr, iou_thr, K)
+    if merged_boxes.dim() != 3 or merged_scores.dim() != 3 or merged_boxes.shape[:2] != merged_scores.shape[:2] or \
+            merged_boxes.shape[2] != 4 * (merged_scores.shape[2] - 1):
+        raise PswinError(f"multiclass_nms_boxes_batch: boxes [B, R, 4 C] and scores [B, R, C + 1], got {tuple(merged_boxes.shape)}, "
+                         f"{tuple(merged_scores.shape)}")
+    B, R, C = int(merged_scores.shape[0]), int(merged_scores.shape[1]), int(merged_scores.shape[2]) - 1
+    dev = merged_boxes.device
+    if roi_count.dtype != torch.int32 or tuple(roi_count.shape) != (B,) or roi_count.device != dev:
+        raise PswinError("multiclass_nms_boxes_batch: roi_count must be an int32 [B] tensor on the device of the boxes")
+    mb, ms, roi_count = merged_boxes.detach().float().contiguous(), merged_scores.detach().float().contiguous(), roi_count.contiguous()
+    nbytes = int(_lib.load().pswin_multiclass_nms_workspace(B, R, C))
+    _lib.check(min(nbytes, 0), "pswin_multiclass_nms_workspace")
+    key = ("detect_ws", B, R, C, _dev_key(dev))
+    if key not in _CACHE:
+        _CACHE[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    keys = torch.empty(B, C, R, dtype=torch.float32, device=dev)
+    call("pswin_multiclass_nms_scores_boxes", mb, ptr(ms), ptr(roi_count), B, R, C, ctypes.c_float(float(score_thr)), ptr(keys))
+    skeys, sidx = torch.sort(keys, dim=-1, descending=True, stable=True)                  # equal scores: ascending proposal
+    final = torch.empty(B, R * C, dtype=torch.float32, device=dev)
+    call("pswin_multiclass_nms_boxes", mb, ptr(skeys), ptr(sidx), ptr(mb), B, R, C, ctypes.c_float(float(iou_thr)), ptr(final), ptr(_CACHE[key]))
+    tkeys, tidx = torch.sort(final, dim=-1, descending=True, stable=True)                 # equal scores: ascending r * C + c
+    K = int(K)
+    boxes, scores, labels, count, source = _aug_out(out, "multiclass_nms_boxes_batch", dev, ((B, K, 4), torch.float32), ((B, K), torch.float32),
+                                                    ((B, K), torch.int64), ((B,), torch.int32), ((B, K), torch.int32))
+    call("pswin_multiclass_nms_select_boxes", mb, ptr(tkeys), ptr(tidx), R * C, min(K, R * C), ptr(mb), B, R, C, K, ptr(boxes), ptr(scores),
+         ptr(labels), ptr(source), ptr(count))
+    return boxes, scores, labels, count, source
+
+
+def paste_masks_aug(logit_list, flips, labels, boxes, count, thr, out_hw, out=None):
+    """paste_masks of tta.merge_aug_masks(logit_list, flips, labels) in one launch (pswin_paste_masks_aug): uint8 [B, K, H, W].  logit_list:
+    up to 24 tensors [B K, C, 28, 28] of one dtype (f32 or bf16), each in any dense layout (its strides are passed on); flips: one bool
+    per source.  The merged probability is never written to memory.  Everything else as paste_masks.  CPU tensors: the definition."""
+    logit_list, flips = list(logit_list), [bool(f) for f in flips]
+    if not logit_list[0].is_cuda:
+        from . import detector, tta
+        prob = tta.merge_aug_masks(logit_list, flips, labels)
+        B, K = labels.shape
+        res = torch.zeros(B, K, int(out_hw[0]), int(out_hw[1]), dtype=torch.uint8)
+        for b, n in enumerate(count.tolist()):
+            if n:
+                res[b, :n] = detector.paste_masks(prob.reshape(B, K, 28, 28)[b, :n], boxes[b, :n].float(), int(out_hw[0]), int(out_hw[1]), thr)
+        return res if out is None else out.copy_(res)
+    N = len(logit_list)
+    if not 1 <= N <= 24 or len(flips) != N:
+        raise PswinError(f"paste_masks_aug: 1 to 24 mask sources and one flip flag each, got {N} and {len(flips)}")
+    H, W = int(out_hw[0]), int(out_hw[1])
+    B, K, C = int(labels.shape[0]), int(labels.shape[1]), int(logit_list[0].shape[1])
+    dev = logit_list[0].device
+    dt = logit_list[0].dtype if logit_list[0].dtype in (torch.float32, torch.bfloat16) else torch.float32
+    srcs = []
+    for l in logit_list:
+        if l.dim() != 4 or tuple(l.shape) != (B * K, C, 28, 28) or l.device != dev:
+            raise PswinError(f"paste_masks_aug: every source is [B K, C, 28, 28] = {(B * K, C, 28, 28)} on one device, got {tuple(l.shape)}")
+        l = l.detach().to(dt)
+        srcs.append(l if min(l.stride()) >= 1 else l.contiguous())
+    if labels.dim() != 2 or tuple(boxes.shape) != (B, K, 4) or count.dtype != torch.int32 or tuple(count.shape) != (B,) or count.device != dev or \
+            labels.dtype != torch.int64:
+        raise PswinError("paste_masks_aug: labels int64 [B, K], boxes [B, K, 4], count int32 [B] on the device of the logits")
+    labels, boxes, count = labels.contiguous(), boxes.detach().float().contiguous(), count.contiguous()
+    if out is None:
+        out = torch.empty(B, K, H, W, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, K, H, W) or not out.is_contiguous() or out.device != dev:
+        raise PswinError(f"paste_masks_aug: out must be a contiguous uint8 [{B}, {K}, {H}, {W}] tensor on the device of the logits")
+    st = _lib.AugMaskSources()
+    st.count = N
+    for i, (l, f) in enumerate(zip(srcs, flips)):
+        st.logits[i], st.flip[i] = l.data_ptr(), int(f)
+        st.stride_n[i], st.stride_c[i], st.stride_y[i], st.stride_x[i] = (int(v) for v in l.stride())
+    call("pswin_paste_masks_aug", srcs[0], ctypes.byref(st), dtype_code(srcs[0]), ptr(labels), ptr(boxes), ptr(count), B, K, C, H, W,
+         ctypes.c_float(float(thr)), ptr(out), algo_bytes=B * K * H * W)
+    return out
+
+
 def roi_targets_ranked(gt_inds, key, cand, gt, gt_labels, num_classes, n_pos_max, n_tot, stds):
     """cascade.roi_targets_ranked on the GPU: roi_targets' five results and pos_rank int64 [B, n_pos_max], the ranks they were drawn by
     (pswin_sample_ranks once, then one launch of pswin_roi_targets on those ranks).  Arguments and limits as roi_targets; capturable as

@@ -859,3 +859,46 @@ class PanoTrainTransform:
             if n_in[b]:
                 src[b, :n_in[b]].copy_(m)
         return src
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# test-time views (MultiScaleFlipAug)
+# ------------------------------------------------------------------------------------------------------------------------------
+def test_view_geometry(ori_hw, img_scales, flip=False):
+    """The tta.View list of MultiScaleFlipAug(img_scale=img_scales, flip=flip) on H x W images (mmdet/datasets/pipelines/test_time_aug.py:
+    for every scale the unflipped view, then the flipped one): img_hw = rescale_size(H, W, scale), scale_factor = (w / W, h / H, w / W,
+    h / H) as float32 (Resize._resize_img)."""
+    from .tta import View
+    H, W = int(ori_hw[0]), int(ori_hw[1])
+    views = []
+    for scale in img_scales:
+        h, w = rescale_size(H, W, scale)
+        sf = (float(np.float32(w / W)), float(np.float32(h / H)))
+        for f in ([False, True] if flip else [False]):
+            views.append(View((h, w), sf + sf, f))
+    return views
+
+
+def test_views(imgs_u8, img_scales, flip=False, mean=IMG_NORM_MEAN, std=IMG_NORM_STD, to_rgb=True, size_divisor=32):
+    """The V view batches of a uint8 [B, H, W, 3] batch and their tta.View: (list of V float32 [B, 3, Hp_v, Wp_v], list of V View), what
+    model.aug_test takes.  Existing kernels only: a flipped view is pano_warp with nothing but the flip flag, then resize_normalize_pad to
+    rescale_size -- the images of a batch share one size, so one View serves them all.
+
+    PARITY: unpinned for the flipped views.  The reference resizes first and flips second (Resize, then RandomFlip); here the flip comes
+    first.  With the project's own restatement of the resize (tests/_pano_ref.py resize_u8_f32) on random bytes the two orders give the same
+    bytes at 64 x 128 -> 32 x 64, 64 x 128 -> 43 x 85 and 100 x 200 -> 64 x 128, and differ by one grey level in 2.7 % of the values at
+    64 x 128 -> 96 x 192, 0.04 % at 128 x 256 -> 85 x 171 and 0.2 % at 512 x 1024 -> 400 x 800: the float32 source coordinate of a mirrored
+    column is not the mirror of the column's.  The unflipped views are resize_normalize_pad as it is pinned elsewhere."""
+    _check_images(imgs_u8, "test_views", (3,))
+    B, H, W, _ = imgs_u8.shape
+    views = test_view_geometry((H, W), img_scales, flip)
+    flipped = None
+    batches = []
+    for v in views:
+        src = imgs_u8
+        if v.flip:
+            if flipped is None:
+                flipped = pano_warp(imgs_u8, make_pano_params([False] * B, [1.0] * B, [1.0] * B, None, [True] * B, W))
+            src = flipped
+        batches.append(resize_normalize_pad(src, [v.img_hw] * B, mean, std, to_rgb, size_divisor))
+    return batches, views
