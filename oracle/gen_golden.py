@@ -114,6 +114,46 @@ def gen_geometry(ns):
     save("geometry", **out)
 
 
+# tests/_geom_cases.py carries the same two lists: the grids the LAST stage of a small input runs on (a pano map smaller than one
+# window, antipodal tokens in one window for H <= 6, planar H < 7: the roll happens inside the padding), at every shift 0..6
+SMALL_PANO = [(1, 2), (2, 4), (3, 5), (3, 6), (4, 7), (4, 8), (5, 9), (5, 10), (6, 11), (6, 12), (7, 13), (7, 14), (8, 16)]
+SMALL_PLANAR = [(1, 1), (2, 4), (4, 7), (6, 6), (7, 7), (7, 8), (8, 13), (14, 15)]
+
+
+def gen_small_grids(hot):
+    """small_grids.npz: window maps (and inverses), planar masks, uv grids and per-window uv of the small grids, built exactly as
+    gen_index_maps / gen_geometry build them for the large ones; int32 maps, int8 masks, f32 uv."""
+    out = {}
+    for (H, W) in SMALL_PANO:
+        out[f"uv_{H}x{W}"] = hot.make_uv_hw2(H, W)
+        for s in range(7):
+            blk = hot.PanoSwinTransformerBlock(dim=32, num_heads=1, window_size=7, shift_size=s, pano_mode=True)
+            ids = (torch.arange(H * W, dtype=torch.float32) + 1).view(1, H, W, 1)
+            t = blk.window_transition(ids, reverse=False)
+            _, SH, SW, _ = t.shape
+            win = hot.window_partition(blk.pad_x(t, SH, SW), 7)
+            out[f"pano_{H}x{W}_s{s}"] = (win.reshape(-1).long() - 1).to(torch.int32)
+            Hp, Wp = blk.pad_x(t, SH, SW).shape[1:3]
+            slots = torch.arange(win.numel(), dtype=torch.float32).view(-1, 7, 7, 1)
+            back = hot.window_reverse(slots, 7, Hp, Wp)[:, :SH, :SW, :].contiguous()
+            back = blk.window_transition(back, reverse=True)
+            out[f"pano_inv_{H}x{W}_s{s}"] = back.reshape(-1).long().to(torch.int32)
+            if s in (0, 3):
+                t = blk.window_transition(hot.make_uv_hw2(H, W)[None], reverse=False)
+                out[f"uvwin_{H}x{W}_s{s}"] = hot.window_partition(blk.pad_x(t, t.shape[1], t.shape[2]), 7).reshape(-1, 49, 2)
+    for (H, W) in SMALL_PLANAR:
+        for s in range(7):
+            blk = hot.PanoSwinTransformerBlock(dim=32, num_heads=1, window_size=7, shift_size=s, pano_mode=False)
+            ids = (torch.arange(H * W, dtype=torch.float32) + 1).view(1, H, W, 1)
+            t = blk.window_transition(blk.pad_x(ids, H, W), reverse=False)
+            out[f"planar_{H}x{W}_s{s}"] = (hot.window_partition(t, 7).reshape(-1).long() - 1).to(torch.int32)
+            if s:
+                layer = hot.BasicLayer(dim=32, depth=2, num_heads=1, window_size=7, pano_mode=False)
+                layer.shift_size = s              # _get_attention_mask reads the layer's shift (HOT:615, 669-675), not the block's
+                out[f"mask_{H}x{W}_s{s}"] = layer._get_attention_mask(torch.zeros(1, H * W, 34), H, W).to(torch.int8)
+    save("small_grids", **out)
+
+
 def gen_window_attention(hot):
     out = {}
     dim, heads, nW, B = 64, 2, 3, 2
@@ -218,13 +258,17 @@ def live_ref_model(ns, cfg, pano):
     return m
 
 
-def gen_oracle_vs_reference(ns):
-    """oracle_vs_reference.npz (outputs / gradients, key "<case>:<what>") and reference_interface.json (the constructor's
-    parameters and defaults, the registry, state-dict keys / shapes / dtypes of the product's configurations)."""
+# the same for the inputs whose last stage is 3 x 6 and 5 x 10 tokens (antipodal tokens in one window, a map smaller than a window): a
+# fixture of their own, oracle_vs_reference_small.npz, so that oracle_vs_reference.npz stays as it is
+LIVE_CASES_SMALL = [(TINY, True, (1, 3, 96, 192)), (TINY, True, (1, 3, 160, 320))]
+
+
+def live_cases(ns, cases):
+    """{"<case>:<what>": array} of the reference's outputs and gradients on the given (cfg, pano, shape) cases."""
     import json
     import panoswin_oracle as po
     out = {}
-    for cfg, pano, shape in LIVE_CASES:
+    for cfg, pano, shape in cases:
         c = live_case_key(cfg, pano, shape)
         out[f"{c}:config"] = np.array(json.dumps(dict(cfg=cfg, pano=pano, shape=list(shape)), sort_keys=True))
         ref = live_ref_model(ns, cfg, pano)
@@ -260,7 +304,14 @@ def gen_oracle_vs_reference(ns):
         out[f"{c}:grad_max"] = np.array(gmax, np.float64)
         out[f"{c}:grad_norm"] = np.array(gnorm, np.float64)
         out[f"{c}:grad_none"] = np.array(none, np.int8)
-    save("oracle_vs_reference", **out)
+    return out
+
+
+def gen_oracle_vs_reference(ns):
+    """oracle_vs_reference.npz (outputs / gradients, key "<case>:<what>") and reference_interface.json (the constructor's
+    parameters and defaults, the registry, state-dict keys / shapes / dtypes of the product's configurations)."""
+    import json
+    save("oracle_vs_reference", **live_cases(ns, LIVE_CASES))
 
     import inspect
     sig = inspect.signature(ns.SimplePanoSwinTransformer.__init__).parameters
@@ -290,7 +341,9 @@ def main():
     jobs = {
         "index_maps": lambda: gen_index_maps(ns.hot),
         "oracle_vs_reference": lambda: gen_oracle_vs_reference(ns),
+        "oracle_vs_reference_small": lambda: save("oracle_vs_reference_small", **live_cases(ns, LIVE_CASES_SMALL)),
         "geometry": lambda: gen_geometry(ns),
+        "small_grids": lambda: gen_small_grids(ns.hot),
         "window_attention": lambda: gen_window_attention(ns.hot),
         "tiny_pano": lambda: save("tiny_pano", **run_model(ns, TINY, True, (2, 3, 64, 128), "tiny")),
         "tiny_planar": lambda: save("tiny_planar", **run_model(ns, TINY, False, (2, 3, 64, 128), "tiny")),

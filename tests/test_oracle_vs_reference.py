@@ -1,5 +1,6 @@
 """The CPU oracle against the reference, through what the reference computed on the same models and inputs (fixtures written by
-oracle/gen_golden.py oracle_vs_reference: tests/golden/oracle_vs_reference.npz and reference_interface.json)."""
+oracle/gen_golden.py oracle_vs_reference: tests/golden/oracle_vs_reference.npz and reference_interface.json; the inputs whose last
+stage is 3 x 6 and 5 x 10 tokens lie in oracle_vs_reference_small.npz, written by oracle_vs_reference_small)."""
 import json
 import os
 
@@ -34,9 +35,10 @@ def _interface():
 
 
 @pytest.mark.parametrize("cfg,pano,shape", [(TINY, True, (2, 3, 64, 128)), (TINY, False, (1, 3, 60, 100)),
-                                            (TINY_PITCH, True, (2, 3, 64, 128)), (TINY, True, (1, 3, 100, 196))])
+                                            (TINY_PITCH, True, (2, 3, 64, 128)), (TINY, True, (1, 3, 100, 196)),
+                                            (TINY, True, (1, 3, 96, 192)), (TINY, True, (1, 3, 160, 320))])
 def test_same_outputs_and_grads(cfg, pano, shape):
-    gold = golden("oracle_vs_reference")
+    gold = golden("oracle_vs_reference_small" if shape[2] in (96, 160) else "oracle_vs_reference")
     c = _case(gold, cfg, pano, shape)
     # the reference ran with the weights det_fill_module(.., "live") gives the oracle (the generator checks the state dicts are equal)
     ora = build_filled(po.SimplePanoSwinTransformerOracle, cfg, pano, "live")
