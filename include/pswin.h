@@ -1152,6 +1152,25 @@ int pswin_eval_match(const float* iou, const float* det_scores, const long long*
 int pswin_ap_segments(const unsigned char* marks_sorted, const int* bounds, const int* num_gts, int T, int S, int C, long long N, float* ap,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Proposal recall of a padded batch (csrc/pswin_recall.hip; evaluation.py: proposal_round_ious, recall_hits, RecallAccumulator)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The reference's eval_recalls on a Proposals (prop_boxes f32 [B][R][4], prop_count int32 [B]) and a PaddedTargets (gt_boxes f32 [B][G][4],
+ * gt_count int32 [B]; ignore uint8 [B][G] or NULL), read in place with both counts from the device, clamped into [0, R] / [0, G]; rows past
+ * a count are never read.  proposal_nums: Kn ints >= 1 and iou_thrs: T DOUBLES in (0, 1], both HOST arrays read during the call.
+ * Per (k, image): the rows are the image's boxes inside its count that are not ignored, the columns its first min(count, proposal_nums[k])
+ * proposals; the IoU is bbox_overlaps' float32 expression (pswin_box_iou_pairs').  Round j takes the largest IoU among the live rows and
+ * columns (ties: the lowest row, inside it the lowest column), stores it in rounds[k][b][j] and deletes that row and that column; rounds
+ * after the columns ran out store -1, an image without columns stores 0 in all its rounds, slots past the number of rows hold -2.
+ * Every element of rounds f32 [Kn][B][G] is written by plain stores.  hits int64 [Kn][T] GAINS the number of rounds with double(value) >=
+ * iou_thrs[t], num_gts int64 [1] the number of rows of the batch (integer atomic adds: no order); the caller clears both.
+ * One workgroup per (k, image), one launch, no host synchronisation.  1 <= B <= 65535, 1 <= R <= 2048, 1 <= G <= 512, 1 <= Kn <= 8,
+ * 1 <= T <= 16, 16-byte aligned boxes, 8-byte aligned hits / num_gts; anything else is PSWIN_ERR_ARG, checked before the device is touched. */
+int pswin_recall_match(const float* prop_boxes, const int* prop_count, const float* gt_boxes, const int* gt_count,
+                       const unsigned char* ignore, const int* proposal_nums, int Kn, const double* iou_thrs, int T, int B, int R, int G,
+                       float* rounds, long long* hits, long long* num_gts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -338,18 +338,10 @@ class MiniCascadeRCNN(det.MiniMaskRCNN):
         from ._lib import PswinError
         if rescale and (scale_factor is None or (with_masks and ori_hw is None)):
             raise PswinError("heads_predict: rescale=True needs scale_factor [B, 4] and, with masks, ori_hw=(H, W)")
-        rpn_cfg, cfg = self.test_cfg["rpn"], self.test_cfg["rcnn"]
-        if self.channels_last:
-            feats = [f.contiguous(memory_format=torch.channels_last) for f in feats]
+        cfg = self.test_cfg["rcnn"]
         auto = dict(device_type="cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda)
-        with torch.autocast(**auto):
-            fpn = self.neck([f for f in feats])
-            rpn_outs = self.rpn(fpn)
-        anchors = det.make_anchors([f.shape[2:] for f in fpn], self.STRIDES, feats[0].device)
-        cls_all, reg_all = self._rpn_flatten(rpn_outs)
-        B, C, K = cls_all.shape[0], self.num_classes, cfg["max_per_img"]
-        rois, _, roi_count = self.proposals(cls_all, reg_all, anchors, rpn_cfg, img_hw)
-        R = rois.shape[1]
+        fpn, rois, _, roi_count = self._test_proposals(feats, img_hw)
+        B, R, C, K = rois.shape[0], rois.shape[1], self.num_classes, cfg["max_per_img"]
         rois_s, cls_s, reg_s = [rois], [], []
         for i in range(self.NUM_STAGES):
             with torch.autocast(**auto):

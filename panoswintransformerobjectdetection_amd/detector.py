@@ -535,6 +535,20 @@ class Detections:
         return out
 
 
+class Proposals:
+    """The RPN's proposals of a batch in tensors of a fixed shape: boxes f32 [B, R, 4], scores f32 [B, R], count int32 [B] ON THE DEVICE.
+    The first count[b] rows of image b are the survivors of the RPN's NMS, in descending score; what follows them is not a proposal."""
+
+    def __init__(self, boxes, scores, count):
+        self.boxes, self.scores, self.count = boxes, scores, count
+
+    def as_lists(self):
+        """Per image an ndarray (count, 5) of x1, y1, x2, y2, score, what the reference's RPN.simple_test returns -- reads back: not for
+        a captured step."""
+        rows = torch.cat([self.boxes.float(), self.scores.float()[:, :, None]], 2).cpu().numpy()
+        return [rows[b, :max(0, min(n, rows.shape[1]))] for b, n in enumerate(self.count.tolist())]
+
+
 def multiclass_nms_batch(rois, roi_count, cls, deltas, stds, img_hw, scale_factor, score_thr, iou_thr, K):
     """detect_post for a batch.  On the GPU: HIP kernels for the whole batch that read the proposal counts from the device
     (ops.multiclass_nms_batch -> pswin_multiclass_nms), so a captured call follows the buffers; on the CPU: the definition."""
@@ -844,6 +858,35 @@ class MiniMaskRCNN(nn.Module):
         return self.heads_loss(self.backbone(img), targets, img.shape[2:])
 
     # -- inference ------------------------------------------------------------------------------------------------------
+    def _test_proposals(self, feats, img_hw):
+        """What every test path starts with: the neck, the RPN head and the proposals under test_cfg["rpn"] -> (fpn, rois f32 [B, R, 4],
+        scores f32 [B, R], count int32 [B])"""
+        if self.channels_last:
+            feats = [f.contiguous(memory_format=torch.channels_last) for f in feats]
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):
+            fpn = self.neck([f for f in feats])
+            rpn_outs = self.rpn(fpn)
+        anchors = make_anchors([f.shape[2:] for f in fpn], self.STRIDES, feats[0].device)
+        cls_all, reg_all = self._rpn_flatten(rpn_outs)
+        rois, scores, count = self.proposals(cls_all, reg_all, anchors, self.test_cfg["rpn"], img_hw)
+        return fpn, rois, scores, count
+
+    @torch.no_grad()
+    def heads_propose(self, feats, img_hw, scale_factor=None, rescale=False):
+        """The RPN alone at test time (RPN.simple_test, detectors/rpn.py:96-114): a Proposals with R = test_cfg rpn max_per_img rows per
+        image at most.  rescale=True: the boxes are divided by scale_factor f32 [B, 4] (w, h, w, h), as the reference does.  No host
+        synchronisation, no data-dependent shape: the call can be captured and replayed, alone or with RecallAccumulator.update."""
+        from ._lib import PswinError
+        if rescale and scale_factor is None:
+            raise PswinError("heads_propose: rescale=True needs scale_factor [B, 4]")
+        _, rois, scores, count = self._test_proposals(feats, img_hw)
+        return Proposals(rois / scale_factor[:, None, :] if rescale else rois, scores, count)
+
+    @torch.no_grad()
+    def simple_test_rpn(self, img, **kw):
+        """backbone + heads_propose: a Proposals for the batch"""
+        return self.heads_propose(self.backbone(img), img.shape[2:], **kw)
+
     @torch.no_grad()
     def heads_predict(self, feats, img_hw, scale_factor=None, rescale=False, with_masks=True, return_raw=False, ori_hw=None):
         """Everything behind the backbone at test time (two_stage.py:217 simple_test; test_mixins.py simple_test_bboxes / simple_test_mask):
@@ -856,17 +899,9 @@ class MiniMaskRCNN(nn.Module):
         from ._lib import PswinError
         if rescale and (scale_factor is None or (with_masks and ori_hw is None)):
             raise PswinError("heads_predict: rescale=True needs scale_factor [B, 4] and, with masks, ori_hw=(H, W)")
-        rpn_cfg, cfg = self.test_cfg["rpn"], self.test_cfg["rcnn"]
-        if self.channels_last:
-            feats = [f.contiguous(memory_format=torch.channels_last) for f in feats]
-        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):
-            fpn = self.neck([f for f in feats])
-            rpn_outs = self.rpn(fpn)
-        anchors = make_anchors([f.shape[2:] for f in fpn], self.STRIDES, feats[0].device)
-        cls_all, reg_all = self._rpn_flatten(rpn_outs)
-        B, C, K = cls_all.shape[0], self.num_classes, cfg["max_per_img"]
-        rois, _, roi_count = self.proposals(cls_all, reg_all, anchors, rpn_cfg, img_hw)           # [B, R, 4]; the survivors of the RPN's NMS lead
-        R = rois.shape[1]
+        cfg = self.test_cfg["rcnn"]
+        fpn, rois, _, roi_count = self._test_proposals(feats, img_hw)                             # [B, R, 4]; the survivors of the RPN's NMS lead
+        B, R, C, K = rois.shape[0], rois.shape[1], self.num_classes, cfg["max_per_img"]
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):
             x = self.roi_align(fpn[:4], self.STRIDES[:4], rois, 7)
             cls, reg = self.bbox_head(x.to(feats[0].dtype))

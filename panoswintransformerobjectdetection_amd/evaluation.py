@@ -26,7 +26,21 @@ the bit).  Scores must be positive floats: the global order sorts their bit patt
 MASKS.  The reference has no mask path (its COCO route needs pycocotools).  The "segm" metric here is this project's choice: the same
 matching rule on the IoU of the full-resolution bitmaps, a pixel counting where its byte is not zero, areas being pixel counts.
 
-Only mode='area' and tpfp_default are in scope; '11points', tpfp_imagenet and proposal recall are not.
+Only mode='area' and tpfp_default are in scope; '11points' and tpfp_imagenet are not.
+
+PROPOSAL RECALL.  The reference measures the RPN alone with mmdet/core/evaluation/recall.py (evaluate(metric='proposal_fast') ->
+fast_eval_recall -> eval_recalls): per image and per proposal number N, the regular ground-truth boxes are matched to the first N
+proposals greedily and ONE TO ONE -- this match IS sequential: every round takes the largest IoU left, records it, and deletes its box
+and its proposal -- and the recall at a threshold is the share of boxes whose recorded IoU reaches it.  `proposal_round_ious` states the
+rounds (ties: the lowest box, then the lowest proposal; which proposal an equal IoU takes decides what later rounds still have, so it is
+part of the contract), `recall_hits` the count, `RecallAccumulator` runs both over a data set, on the GPU as one HIP launch per batch
+that reads a Proposals and a PaddedTargets in place (csrc/pswin_recall.hip).  Pinned to the reference's own results, rounds bit for bit:
+tests/golden/recall.npz, tools/gen_recall_golden.py.
+
+    acc = RecallAccumulator(proposal_nums=(100, 300, 1000), device="cuda")
+    for batch in loader:
+        acc.update(model.simple_test_rpn(img), targets)   # no host synchronisation; may be captured with the proposals
+    result = acc.summarize()                              # reads back: recalls f64 [Kn, T], ar f64 [Kn], num_gts
 """
 import ctypes
 
@@ -35,7 +49,7 @@ import torch
 
 from . import _lib
 from ._lib import PswinError
-from .detector import Detections, PaddedTargets
+from .detector import Detections, PaddedTargets, Proposals
 
 MARK_IGNORED, MARK_TP, MARK_FP = 0, 1, 2
 AP_CHUNK = 1024           # records one workgroup of pswin_ap_segments takes per trip (pswin_ap_segments_chunk(); tests aim at it)
@@ -461,3 +475,183 @@ class MapAccumulator:
             if has[s].any():
                 mean_ap[:, s] = ap[:, s, has[s]].double().mean(1).float()
         return dict(mean_ap=mean_ap, ap=ap, num_gts=num_gts, num_dets=bounds[1:] - bounds[:-1])
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# proposal recall: definitions (any device)
+# ------------------------------------------------------------------------------------------------------------------------
+RECALL_MAX_G, RECALL_MAX_R = 512, 2048          # boxes and proposals per image one workgroup of pswin_recall_match keeps in LDS
+DEFAULT_RECALL_THRS = np.arange(0.5, 0.96, 0.05)
+
+
+def _thresholds(iou_thrs):
+    """float64 [T] of a number, a sequence or an array, every value as it came"""
+    return np.atleast_1d(np.asarray(iou_thrs, dtype=np.float64)).reshape(-1)
+
+
+def box_iou_matrix(rows, cols):
+    """f32 [g, n] of boxes [g, 4] and [n, 4]: box_iou_pairs' expression without counts and labels.  Symmetric in its operands bit for bit
+    (float addition, max and min commute), so the reference's exchange of the operands when there are more rows than columns is
+    invisible."""
+    r, c = rows.float()[:, None, :], cols.float()[None, :, :]
+    xs, ys = torch.maximum(r[..., 0], c[..., 0]), torch.maximum(r[..., 1], c[..., 1])
+    xe, ye = torch.minimum(r[..., 2], c[..., 2]), torch.minimum(r[..., 3], c[..., 3])
+    overlap = (xe - xs).clamp(min=0) * (ye - ys).clamp(min=0)
+    return overlap / (box_areas(rows)[:, None] + box_areas(cols)[None, :] - overlap).clamp(min=1e-6)
+
+
+def greedy_rounds(iou):
+    """f32 [g] of iou f32 [g, n]: round j's IoU.  Every round takes, among the live rows and live columns, every row's largest entry at
+    its lowest column, then the lowest row among the largest of those; it records the value and deletes the row and the column.  Rounds
+    j >= n > 0 record -1; n == 0 records 0 in every round."""
+    g, n = iou.shape
+    rec = iou.new_zeros(g)
+    if n == 0 or g == 0:
+        return rec
+    live_r, live_c = torch.ones(g, dtype=torch.bool, device=iou.device), torch.ones(n, dtype=torch.bool, device=iou.device)
+    gone = iou.new_full((), float("-inf"))
+    for j in range(g):
+        if j >= n:
+            rec[j:] = -1.0
+            break
+        m = torch.where(live_r[:, None] & live_c[None, :], iou, gone)
+        col = m.argmax(1)                                  # argmax: the first of equal maxima
+        best = m.gather(1, col[:, None])[:, 0]
+        r = best.argmax()
+        rec[j] = best[r]
+        live_r[r], live_c[col[r]] = False, False
+    return rec
+
+
+def proposal_round_ious(props, gts, proposal_nums, ignore=None):
+    """f32 [Kn, B, Gmax]: out[k, b, j] is the IoU that round j of the greedy one-to-one matching records (greedy_rounds) for image b with
+    its first n = min(clamp(props.count[b], 0, R), proposal_nums[k]) proposals as columns and, as rows, its boxes inside gts.count[b] that
+    `ignore` (bool [B, Gmax] or None) does not flag, in their order.  The index is the ROUND, not the box.  There is no label test:
+    proposals have no class.  Slots past the number of rows hold -2.  Reads the counts back (a definition, not for a captured step)."""
+    (B, R), G = props.scores.shape, gts.boxes.shape[1]
+    nums = [int(v) for v in proposal_nums]
+    out = torch.full((len(nums), B, G), -2.0, dtype=torch.float32, device=props.boxes.device)
+    for b, (npr, ng) in enumerate(zip(props.count.tolist(), gts.count.tolist())):
+        npr, ng = max(0, min(npr, R)), max(0, min(ng, G))
+        rows = gts.boxes[b, :ng].float()
+        if ignore is not None:
+            rows = rows[~ignore[b, :ng].bool()]
+        if rows.shape[0] == 0:
+            continue
+        iou = box_iou_matrix(rows, props.boxes[b, :npr])
+        for k, num in enumerate(nums):
+            out[k, b, :rows.shape[0]] = greedy_rounds(iou[:, :max(0, min(npr, num))])
+    return out
+
+
+def _recall_hits(rounds, iou_thrs):
+    """(hits int64 [Kn, T], num_gts int64 0-dim) as tensors on rounds' device"""
+    thr = torch.as_tensor(_thresholds(iou_thrs), device=rounds.device)
+    real = rounds > -2
+    hit = (rounds.double()[..., None] >= thr) & real[..., None]
+    return hit.sum((1, 2)), real[0].sum()
+
+
+def recall_hits(rounds, iou_thrs):
+    """(hits int64 [Kn, T], num_gts int) of rounds f32 [Kn, B, Gmax]: per (proposal number, threshold) the slots with a value > -2 (a
+    round of a box) and double(value) >= double(threshold); num_gts is the number of such slots of one proposal number.  THE COMPARISON
+    IS IN DOUBLE, on thresholds kept as float64: the reference compares its float32 IoUs with a float64 threshold array, and with
+    np.arange(0.5, 0.96, 0.05) an IoU of exactly 0.65, 0.7, 0.75, 0.9 or 0.95 in float32 is then a miss at the threshold of that name,
+    where a float32 comparison calls it a hit.  This is NOT the float32 comparison match_pairs / MapAccumulator make (tpfp_default
+    compares float32 with a Python float, which numpy keeps in float32)."""
+    hits, num = _recall_hits(rounds, iou_thrs)
+    return hits, int(num)
+
+
+def eval_recalls_lists(gts, proposals, proposal_nums=(100, 300, 1000), iou_thrs=0.5):
+    """The reference's eval_recalls(gts, proposals, proposal_nums, iou_thrs) from the definitions above: float64 [Kn, T].  gts: per
+    image an array (n, 4) or None; proposals: per image (k, 4), taken in their order, or (k, 5) with a score, ordered by descending
+    score -- equal scores keep their order (the project's tie rule; the reference's is a reversed unstable argsort).  The first
+    proposal_nums[-1] are kept.  recalls = hits / float(num_gts) in double: NaN when there is no box at all, as the reference gives."""
+    nums = [int(v) for v in np.atleast_1d(np.asarray(proposal_nums)).reshape(-1)]
+    rows, boxes = [], []
+    for p, g in zip(proposals, gts):
+        p = np.asarray(p)
+        if p.ndim == 2 and p.shape[1] == 5:
+            p = p[np.argsort(-p[:, 4], kind="stable")]
+        rows.append(torch.as_tensor(p.reshape(-1, p.shape[1] if p.ndim == 2 else 4)[:max(nums[-1], 0), :4].astype(np.float32)))
+        boxes.append(torch.zeros(0, 4) if g is None else torch.as_tensor(np.asarray(g, dtype=np.float32)).reshape(-1, 4))
+    B, R, G = len(rows), max(1, max(r.shape[0] for r in rows)), max(1, max(g.shape[0] for g in boxes))
+    props = Proposals(torch.zeros(B, R, 4), torch.zeros(B, R), torch.tensor([r.shape[0] for r in rows], dtype=torch.int32))
+    targets = PaddedTargets(torch.zeros(B, G, 4), torch.zeros(B, G, dtype=torch.long), torch.tensor([g.shape[0] for g in boxes], dtype=torch.int32))
+    for b, (r, g) in enumerate(zip(rows, boxes)):
+        props.boxes[b, :r.shape[0]], targets.boxes[b, :g.shape[0]] = r, g
+    hits, num_gts = recall_hits(proposal_round_ious(props, targets, nums), iou_thrs)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return hits.numpy().astype(np.float64) / np.float64(num_gts)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# proposal recall: the kernel (csrc/pswin_recall.hip) and the accumulator
+# ------------------------------------------------------------------------------------------------------------------------
+def recall_supported(B, R, G, Kn, T):
+    """Whether pswin_recall_match takes the shape: the boxes and proposals of an image fit one workgroup's LDS"""
+    return 1 <= B <= 65535 and 1 <= R <= RECALL_MAX_R and 1 <= G <= RECALL_MAX_G and 1 <= Kn <= 8 and 1 <= T <= 16
+
+
+class RecallAccumulator:
+    """Proposal recall (AR@N) over a data set, batch by batch: hits int64 [Kn, T] and num_gts int64 [1] on `device`.  proposal_nums: Kn
+    numbers >= 1, ascending as the reference expects them; iou_thrs: T thresholds in (0, 1], kept as float64."""
+
+    def __init__(self, proposal_nums=(100, 300, 1000), iou_thrs=DEFAULT_RECALL_THRS, device="cpu"):
+        self.proposal_nums = tuple(int(v) for v in np.atleast_1d(np.asarray(proposal_nums)).reshape(-1))
+        self.iou_thrs = _thresholds(iou_thrs)
+        self.Kn, self.T = len(self.proposal_nums), len(self.iou_thrs)
+        if not (1 <= self.Kn <= 8 and 1 <= self.T <= 16):
+            raise PswinError("RecallAccumulator: 1 to 8 proposal numbers, 1 to 16 thresholds")
+        if any(v < 1 for v in self.proposal_nums) or any(not 0 < t <= 1 for t in self.iou_thrs):
+            raise PswinError(f"RecallAccumulator: proposal numbers >= 1 and thresholds in (0, 1], got {self.proposal_nums}, {self.iou_thrs}")
+        dev = torch.device(device)
+        self.hits = torch.zeros(self.Kn, self.T, dtype=torch.int64, device=dev)
+        self.num_gts = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._nums = (ctypes.c_int * self.Kn)(*self.proposal_nums)
+        self._thrs = (ctypes.c_double * self.T)(*[float(t) for t in self.iou_thrs])
+
+    def reset(self):
+        """Forget every batch, in place (stream-ordered; the buffers keep their addresses for a captured update)."""
+        self.hits.zero_(), self.num_gts.zero_()
+        return self
+
+    def update(self, proposals, targets, ignore=None, out=None):
+        """Score one batch: the rounds f32 [Kn, B, Gmax] (proposal_round_ious), their hits and the batch's boxes added to the accumulators.
+        proposals: a Proposals; targets: a PaddedTargets, or the list form, padded on entry (PaddedTargets.of); ignore: bool [B, Gmax] or
+        None -- flagged boxes are left out before the matching, as fast_eval_recall drops them.  On the GPU inside recall_supported one HIP
+        launch with no host synchronisation and no data-dependent shape, which can be captured with heads_propose (out: its buffer for
+        the rounds, if the caller keeps one); outside it, and on the CPU, the definitions (on the GPU they read the counts back)."""
+        gts = PaddedTargets.of(targets)
+        dev = self.hits.device
+        if proposals.boxes.dim() != 3 or gts.boxes.shape[0] != proposals.boxes.shape[0]:
+            raise PswinError(f"RecallAccumulator.update: proposals {tuple(proposals.boxes.shape)}, targets {tuple(gts.boxes.shape)}")
+        for name, t, dt in (("proposals.boxes", proposals.boxes, torch.float32), ("proposals.count", proposals.count, torch.int32),
+                            ("targets.boxes", gts.boxes, torch.float32), ("targets.count", gts.count, torch.int32)):
+            if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise PswinError(f"RecallAccumulator.update: {name} must be a contiguous {dt} tensor on {dev}")
+        ignore = _flags(ignore, gts)
+        (B, R), G = proposals.boxes.shape[:2], gts.boxes.shape[1]
+        if not (dev.type == "cuda" and recall_supported(B, R, G, self.Kn, self.T)):
+            rounds = proposal_round_ious(proposals, gts, self.proposal_nums, ignore)
+            hits, num = _recall_hits(rounds, self.iou_thrs)
+            self.hits.add_(hits), self.num_gts.add_(num)
+            if out is not None:
+                rounds = _out(out, rounds.shape, torch.float32, dev, "RecallAccumulator.update").copy_(rounds)
+            return rounds
+        rounds = _out(out, (self.Kn, B, G), torch.float32, dev, "RecallAccumulator.update")
+        p = _lib.ptr
+        _lib.call("pswin_recall_match", rounds, p(proposals.boxes), p(proposals.count), p(gts.boxes), p(gts.count), p(ignore), self._nums,
+                  self.Kn, self._thrs, self.T, B, R, G, p(rounds), p(self.hits), p(self.num_gts),
+                  algo_bytes=self.Kn * B * (min(R, max(self.proposal_nums)) * 16 + G * 20))
+        return rounds
+
+    def summarize(self):
+        """Reads back once: dict(recalls f64 [Kn, T] = hits / float(num_gts), NaN without a box; ar f64 [Kn], their mean over the
+        thresholds as fast_eval_recall reports it; num_gts int)."""
+        both = torch.cat([self.hits.reshape(-1), self.num_gts]).cpu().numpy()
+        num_gts = int(both[-1])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            recalls = both[:-1].reshape(self.Kn, self.T).astype(np.float64) / np.float64(num_gts)
+        return dict(recalls=recalls, ar=recalls.mean(axis=1), num_gts=num_gts)
