@@ -353,8 +353,8 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_kernel(AttnArgs a) {
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj) gsum[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // bf16: a second register set holds the next image's operands for a whole iteration (64 VGPRs).  f32 operands
-    // are twice as large, so the f32 (parity) path reuses the one set as soon as the MFMAs have consumed it.
+    // DUAL (off, see above) would keep the next image's operands in a second register set for a whole iteration (64 VGPRs).
+    // As built, every dtype reuses the one set as soon as the dS / dV / dK MFMAs have consumed it, before the stores and dQ.
     for (int r = 0; r < a.reps_per_chunk; ++r) {
         const size_t win = (size_t)(chunk * a.reps_per_chunk + r) * a.nb + wb;
         const size_t row0 = win * TOK;
