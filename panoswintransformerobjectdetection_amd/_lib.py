@@ -99,6 +99,10 @@ _PROTOTYPES = {
     "pswin_multiclass_nms_boxes": [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp],
     "pswin_multiclass_nms_select_boxes": [_vp, _vp, ctypes.c_longlong, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pswin_paste_masks_aug": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp],
+    "pswin_rle_workspace": [ctypes.c_longlong, _i, _i, _vp],
+    "pswin_rle_encode": [_vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp, _vp, ctypes.c_longlong, _vp, _vp],
+    "pswin_paste_masks_rle": [_vp, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i, _i,
+                              _i, _f, _vp, _vp, ctypes.c_longlong, _vp, _vp],
     "pswin_sample_rows_per_workgroup": [],
     "pswin_sample_workspace": [_i, _i, _i],
     "pswin_sample_ranks": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],

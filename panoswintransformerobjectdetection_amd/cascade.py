@@ -328,7 +328,8 @@ class MiniCascadeRCNN(det.MiniMaskRCNN):
 
     # -- inference ------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def heads_predict(self, feats, img_hw, scale_factor=None, rescale=False, with_masks=True, return_raw=False, ori_hw=None):
+    def heads_predict(self, feats, img_hw, scale_factor=None, rescale=False, with_masks=True, return_raw=False, ori_hw=None,
+                      mask_format="bitmap", rle_capacity=None):
         """Everything behind the backbone at test time (cascade_roi_head.py:290-414): a Detections with the parent's keywords.  The
         proposals go through the three stages (argmax class, regress, clip); the class scores are the mean of the three softmaxes
         (ensemble_logits), the boxes the last stage's deltas on the last RoIs, the masks the mean over the three mask heads of the
@@ -336,6 +337,7 @@ class MiniCascadeRCNN(det.MiniMaskRCNN):
         (list of three [B, R, 4]), roi_count [B], cls and deltas (lists of three), mask_logits (list of three [B K, C, 28, 28] or None).
         No host synchronisation, no data-dependent shape: the call can be captured and replayed."""
         from ._lib import PswinError
+        self._check_mask_format(mask_format)
         if rescale and (scale_factor is None or (with_masks and ori_hw is None)):
             raise PswinError("heads_predict: rescale=True needs scale_factor [B, 4] and, with masks, ori_hw=(H, W)")
         cfg = self.test_cfg["rcnn"]
@@ -354,15 +356,15 @@ class MiniCascadeRCNN(det.MiniMaskRCNN):
         sf = scale_factor if rescale else None
         boxes, scores, labels, count, source = self.multiclass_nms(rois_s[-1], roi_count, ensemble_logits(cls_s), reg_s[-1],
                                                                    self.rcnn_cfg[-1]["stds"], img_hw, sf, cfg["score_thr"], cfg["nms"], K)
-        masks = mask_logits = None
+        masks = mask_logits = rle = None
         if with_masks:
             mask_rois = boxes * sf[:, None, :] if rescale else boxes
             with torch.autocast(**auto):
                 xm = self.roi_align(fpn[:4], self.STRIDES[:4], mask_rois, 14).to(feats[0].dtype)
                 mask_logits = [h(xm) for h in self.mask_heads]
-            masks = self.paste(ensemble_mask_logits(mask_logits, labels), torch.zeros_like(labels), boxes, count, cfg["mask_thr_binary"],
-                               ori_hw if rescale else img_hw)
-        out = det.Detections(boxes, scores, labels, count, source, masks)
+            masks, rle = self._paste_outputs(ensemble_mask_logits(mask_logits, labels), torch.zeros_like(labels), boxes, count,
+                                             cfg["mask_thr_binary"], ori_hw if rescale else img_hw, mask_format, rle_capacity)
+        out = det.Detections(boxes, scores, labels, count, source, masks, rle)
         if return_raw:
             return out, dict(rois=rois_s, roi_count=roi_count, cls=cls_s, deltas=reg_s, mask_logits=mask_logits)
         return out

@@ -107,23 +107,13 @@ __global__ __launch_bounds__(PASTE_THREADS) void paste_kernel(const void* __rest
                                                               const int* __restrict__ count, int K, int C, int H, int W, float thr,
                                                               unsigned char* __restrict__ out) {
     __shared__ float prob[PASTE_LD * PASTE_LD];
-    const int b = blockIdx.z, k = blockIdx.y, ybase = blockIdx.x * PASTE_ROWS, t = threadIdx.x;
+    const int b = blockIdx.z, k = blockIdx.y, ybase = blockIdx.x * PASTE_ROWS;
     const size_t det = (size_t)b * K + k;
     const bool live = k < det_clamp(count[b], K);       // the same for the whole workgroup
     f32x4 box = {0.f, 0.f, 0.f, 0.f};
     if (live) {
         box = reinterpret_cast<const f32x4*>(boxes)[det];
-        const long long lab = labels[det];
-        const long long c = lab < 0 ? 0 : (lab > C - 1 ? C - 1 : lab);
-        for (int i = t; i < PASTE_LD * PASTE_LD; i += PASTE_THREADS) {
-            const int yy = i / PASTE_LD - 1, xx = i % PASTE_LD - 1;
-            float v = 0.f;
-            if (yy >= 0 && yy < PASTE_M && xx >= 0 && xx < PASTE_M) {
-                const float l = det_load(logits, DT, (size_t)((long long)det * sn + c * sc + yy * sy + xx * sx));
-                v = 1.f / (1.f + expf(-l));
-            }
-            prob[i] = v;
-        }
+        paste_stage<DT>(prob, logits, sn, sc, sy, sx, det, paste_channel(labels[det], C));
     }
     paste_rows(prob, live, box, det, ybase, H, W, thr, out);
 }

@@ -146,6 +146,47 @@ __device__ inline float paste_coord(float pc, float lo, float hi) {
     return ((g + 1.f) * (float)PASTE_M - 1.f) / 2.f;
 }
 
+// One axis of the bilinear sample at source coordinate i (paste_coord): whether it lies in (-1, 28) -- outside, and for a NaN, the pixel
+// samples nothing -- and, inside, the lower cell f = floor(i) in [-1, 27] with the weights of cells f and f + 1
+struct PasteAxis {
+    bool in;
+    int f;
+    float w0, w1;
+};
+__device__ inline PasteAxis paste_axis(float i) {
+    PasteAxis a = {i > -1.f && i < (float)PASTE_M, 0, 0.f, 0.f};
+    if (a.in) {
+        const float ff = floorf(i);
+        a.f = (int)ff;
+        a.w1 = i - ff;
+        a.w0 = (ff + 1.f) - i;
+    }
+    return a;
+}
+// The sampled probability of a pixel whose two axes are inside: `prob` is the staged tile (paste_stage).  THE per-pixel value of every
+// paste: the bitmap kernels (paste_rows) and the run-length kernel (csrc/pswin_rle.hip) compare it with thr.
+__device__ inline float paste_value(const float* prob, const PasteAxis& ax, const PasteAxis& ay) {
+    const float* q = prob + (ay.f + 1) * PASTE_LD + 1 + ax.f;
+    return q[0] * (ax.w0 * ay.w0) + q[1] * (ax.w1 * ay.w0) + q[PASTE_LD] * (ax.w0 * ay.w1) + q[PASTE_LD + 1] * (ax.w1 * ay.w1);
+}
+
+// The staging of one source: prob (PASTE_LD x PASTE_LD f32 in LDS) = sigmoid(logits[det][c]) inside a zero border, by all PASTE_THREADS
+// threads of the workgroup, NOT synchronised
+template <int DT>
+__device__ inline void paste_stage(float* prob, const void* __restrict__ logits, long long sn, long long sc, long long sy, long long sx,
+                                   size_t det, long long c) {
+    for (int i = threadIdx.x; i < PASTE_LD * PASTE_LD; i += PASTE_THREADS) {
+        const int yy = i / PASTE_LD - 1, xx = i % PASTE_LD - 1;
+        float v = 0.f;
+        if (yy >= 0 && yy < PASTE_M && xx >= 0 && xx < PASTE_M) {
+            const float l = det_load(logits, DT, (size_t)((long long)det * sn + c * sc + yy * sy + xx * sx));
+            v = 1.f / (1.f + expf(-l));
+        }
+        prob[i] = v;
+    }
+}
+__device__ inline long long paste_channel(long long lab, int C) { return lab < 0 ? 0 : (lab > C - 1 ? C - 1 : lab); }
+
 // The rows ybase .. ybase + PASTE_ROWS - 1 of detection `det`: prob is the workgroup's staged tile (PASTE_LD x PASTE_LD f32, zero border),
 // written by all threads and NOT yet synchronised; a detection that is not live writes zeros
 __device__ inline void paste_rows(const float* prob, bool live, f32x4 box, size_t det, int ybase, int H, int W, float thr,
@@ -177,21 +218,12 @@ __device__ inline void paste_rows(const float* prob, bool live, f32x4 box, size_
         }
         unsigned bits = 0u;                             // bit p: pixel xs + p
         if (live) {
-            const float iy = paste_coord((float)y + 0.5f, box[1], box[3]);
-            if (iy > -1.f && iy < (float)PASTE_M) {
-                const float yf = floorf(iy);
-                const float wy1 = iy - yf, wy0 = (yf + 1.f) - iy;
-                const float* pr = prob + ((int)yf + 1) * PASTE_LD + 1;
+            const PasteAxis ay = paste_axis(paste_coord((float)y + 0.5f, box[1], box[3]));
+            if (ay.in) {
 #pragma unroll
                 for (int p = 0; p < 16; ++p) {
-                    const float ix = paste_coord((float)(xs + p) + 0.5f, box[0], box[2]);
-                    float val = 0.f;
-                    if (ix > -1.f && ix < (float)PASTE_M) {
-                        const float xf = floorf(ix);
-                        const float wx1 = ix - xf, wx0 = (xf + 1.f) - ix;
-                        const float* q = pr + (int)xf;
-                        val = q[0] * (wx0 * wy0) + q[1] * (wx1 * wy0) + q[PASTE_LD] * (wx0 * wy1) + q[PASTE_LD + 1] * (wx1 * wy1);
-                    }
+                    const PasteAxis ax = paste_axis(paste_coord((float)(xs + p) + 0.5f, box[0], box[2]));
+                    const float val = ax.in ? paste_value(prob, ax, ay) : 0.f;
                     bits |= (val >= thr ? 1u : 0u) << p;
                 }
             } else {

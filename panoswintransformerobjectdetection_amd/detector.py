@@ -521,10 +521,11 @@ class Detections:
     """The detections of a batch in tensors of a fixed shape, the inference counterpart of PaddedTargets: boxes f32 [B, K, 4], scores f32
     [B, K], labels int64 [B, K], count int32 [B] ON THE DEVICE (the first count[b] rows of image b are detections, in descending score;
     the rest are zeros, masks included), source int32 [B, K] (the flat index r * C + c of each detection: proposal r, class c) and masks
-    uint8 [B, K, H, W] or None (Faster R-CNN)."""
+    uint8 [B, K, H, W] or None (Faster R-CNN).  rle: the masks' COCO run-length encoding (rle.RleMasks) or None --
+    heads_predict(mask_format="rle") fills it and leaves masks None."""
 
-    def __init__(self, boxes, scores, labels, count, source, masks=None):
-        self.boxes, self.scores, self.labels, self.count, self.source, self.masks = boxes, scores, labels, count, source, masks
+    def __init__(self, boxes, scores, labels, count, source, masks=None, rle=None):
+        self.boxes, self.scores, self.labels, self.count, self.source, self.masks, self.rle = boxes, scores, labels, count, source, masks, rle
 
     def as_lists(self):
         """Per image (dets [k, 5], labels [k], masks bool [k, H, W] or None) -- reads the counts back: not for a captured step."""
@@ -532,6 +533,35 @@ class Detections:
         for b, n in enumerate(self.count.tolist()):
             dets = torch.cat([self.boxes[b, :n], self.scores[b, :n, None]], 1)
             out.append((dets, self.labels[b, :n], None if self.masks is None else self.masks[b, :n].bool()))
+        return out
+
+    def as_results(self, num_classes):
+        """Per image what the reference's simple_test followed by encode_mask_results hands to the results file (mmdet/apis/test.py:60,
+        mmdet/core/mask/utils.py:36-63): (bbox_results, segm_results) -- bbox_results a list of num_classes float32 arrays [k_c, 5]
+        (bbox2result, mmdet/core/bbox/transforms.py:99), segm_results a list of num_classes lists of {"size": [H, W], "counts": bytes}
+        (cls_segms[labels[i]].append(...) of fcn_mask_head.py:302: a row's place in its class list follows row order, as in the arrays).
+        The runs come from `rle` when it is set, otherwise from rle.encode_masks(masks, count); without masks only bbox_results.
+        Reads back: not for a captured step."""
+        from . import rle as rle_mod
+        K = self.boxes.shape[1]
+        enc = self.rle
+        if enc is None and self.masks is not None:
+            enc = rle_mod.encode_masks(self.masks.contiguous(), self.count)
+        per_image = None if enc is None else enc.to_lists()
+        rows = torch.cat([self.boxes.float(), self.scores.float()[:, :, None]], 2).cpu().numpy()
+        labels = self.labels.cpu().numpy()
+        out = []
+        for b, n in enumerate(self.count.tolist()):
+            n = max(0, min(int(n), K))
+            lab = labels[b, :n]
+            bbox = [rows[b, :n][lab == c] for c in range(num_classes)]
+            if per_image is None:
+                out.append(bbox)
+                continue
+            segm = [[] for _ in range(num_classes)]
+            for k in range(n):
+                segm[int(lab[k])].append(per_image[b][k])
+            out.append((bbox, segm))
         return out
 
 
@@ -564,6 +594,13 @@ def paste_masks_dispatch(mask_logits, labels, boxes, count, thr, out_hw):
         from . import ops
         return ops.paste_masks(mask_logits, labels, boxes, count, thr, out_hw)
     return paste_masks_batch(mask_logits, labels, boxes, count, thr, out_hw)
+
+
+def paste_masks_rle_dispatch(mask_logits, labels, boxes, count, thr, out_hw, capacity=None):
+    """rle.paste_masks_rle: the RLE of paste_masks_batch.  On the GPU the fused HIP route (ops.paste_masks_rle -> pswin_paste_masks_rle), which
+    never forms the bitmap; on the CPU the definition."""
+    from . import rle
+    return rle.paste_masks_rle(mask_logits, labels, boxes, count, thr, out_hw, capacity)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -713,6 +750,7 @@ class MiniMaskRCNN(nn.Module):
     proposals = staticmethod(proposals_batch_dispatch)    # the RPN's proposals (top nms_pre, decode, NMS, top max_per_img), once per batch
     multiclass_nms = staticmethod(multiclass_nms_batch)   # test time: softmax, decode, class-wise NMS, top K of a batch
     paste = staticmethod(paste_masks_dispatch)            # test time: the detections' masks pasted into the image
+    paste_rle = staticmethod(paste_masks_rle_dispatch)    # test time: the run-length encoding of those masks without the bitmaps
     rpn_loss = staticmethod(losses.rpn_loss_dispatch)     # the RPN's two losses from the flattened outputs and rpn_targets' results
     cls_loss = staticmethod(losses.cls_loss_dispatch)     # the box head's cross-entropy on its logits as they are
     box_loss = staticmethod(losses.box_loss_dispatch)     # the box head's L1 on the deltas of every row's class
@@ -887,16 +925,36 @@ class MiniMaskRCNN(nn.Module):
         """backbone + heads_propose: a Proposals for the batch"""
         return self.heads_propose(self.backbone(img), img.shape[2:], **kw)
 
+    def _paste_outputs(self, mask_logits, labels, boxes, count, thr, out_hw, mask_format, rle_capacity):
+        """(masks, rle) of heads_predict for its mask_format"""
+        if mask_format == "rle":
+            return None, self.paste_rle(mask_logits, labels, boxes, count, thr, out_hw, rle_capacity)
+        masks = self.paste(mask_logits, labels, boxes, count, thr, out_hw)
+        if mask_format == "bitmap":
+            return masks, None
+        from . import rle
+        return masks, rle.encode_masks(masks, count, rle_capacity)
+
+    @staticmethod
+    def _check_mask_format(mask_format):
+        if mask_format not in ("bitmap", "rle", "both"):
+            from ._lib import PswinError
+            raise PswinError(f'heads_predict: mask_format must be "bitmap", "rle" or "both", got {mask_format!r}')
+
     @torch.no_grad()
-    def heads_predict(self, feats, img_hw, scale_factor=None, rescale=False, with_masks=True, return_raw=False, ori_hw=None):
+    def heads_predict(self, feats, img_hw, scale_factor=None, rescale=False, with_masks=True, return_raw=False, ori_hw=None,
+                      mask_format="bitmap", rle_capacity=None):
         """Everything behind the backbone at test time (two_stage.py:217 simple_test; test_mixins.py simple_test_bboxes / simple_test_mask):
         a Detections with K = test_cfg rcnn max_per_img rows per image.  scale_factor: f32 [B, 4] device tensor (w, h, w, h) or None.
         rescale=True: the boxes are divided by it before the NMS, as the reference does, and multiplied back to form the mask RoIs; the
         masks are then pasted at ori_hw (one size for the batch), otherwise at img_hw.  with_masks=False: the Faster R-CNN result.
         return_raw=True: also a dict of the tensors the post-processing consumed -- rois [B, R, 4], roi_count [B], cls [B, R, C + 1],
         deltas [B, R, 4 C], mask_logits [B K, C, 28, 28] -- so that the definitions can be applied to exactly those.
+        mask_format: "bitmap" (masks uint8 [B, K, H, W]), "rle" (masks None, rle = the RleMasks of self.paste_rle with rle_capacity runs --
+        the bitmaps are never formed) or "both".
         No host synchronisation, no host-to-device copy, no data-dependent shape: the call can be captured and replayed."""
         from ._lib import PswinError
+        self._check_mask_format(mask_format)
         if rescale and (scale_factor is None or (with_masks and ori_hw is None)):
             raise PswinError("heads_predict: rescale=True needs scale_factor [B, 4] and, with masks, ori_hw=(H, W)")
         cfg = self.test_cfg["rcnn"]
@@ -909,14 +967,15 @@ class MiniMaskRCNN(nn.Module):
         sf = scale_factor if rescale else None
         boxes, scores, labels, count, source = self.multiclass_nms(rois, roi_count, cls, reg, self.BBOX_STDS, img_hw, sf, cfg["score_thr"],
                                                                    cfg["nms"], K)
-        masks = mask_logits = None
+        masks = mask_logits = rle = None
         if with_masks:
             mask_rois = boxes * sf[:, None, :] if rescale else boxes                              # back at the test scale (test_mixins.py:275-281)
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=feats[0].is_cuda):
                 xm = self.roi_align(fpn[:4], self.STRIDES[:4], mask_rois, 14)
                 mask_logits = self.mask_head(xm.to(feats[0].dtype))                               # [B * K, classes, 28, 28]
-            masks = self.paste(mask_logits, labels, boxes, count, cfg["mask_thr_binary"], ori_hw if rescale else img_hw)
-        out = Detections(boxes, scores, labels, count, source, masks)
+            masks, rle = self._paste_outputs(mask_logits, labels, boxes, count, cfg["mask_thr_binary"], ori_hw if rescale else img_hw,
+                                             mask_format, rle_capacity)
+        out = Detections(boxes, scores, labels, count, source, masks, rle)
         if return_raw:
             return out, dict(rois=rois, roi_count=roi_count, cls=cls, deltas=reg, mask_logits=mask_logits)
         return out

@@ -77,7 +77,8 @@ definitions bit for bit.
     the right; for each of np.linspace(0, 1, 101) the precision at the first index with rc >= r (searchsorted, side='left'), or 0.
  7. SUMMARIZE, in numpy on the host: each statistic is the mean over the entries > -1, or -1: AP over all t (range 0, last m), at t = 0.5
     and 0.75 (found with np.isclose), for ranges 1, 2, 3; AR for range 0 at each of the first three max_dets, for ranges 1, 2, 3 at the
-    last.  COCOeval's `scores` array, the 'proposal' route (useCats = 0), RLE and JSON files are out of scope.
+    last.  COCOeval's `scores` array, the 'proposal' route (useCats = 0) and JSON files are out of scope; the masks' RLE for
+    results files is rle.py (Detections.as_results), and the mask IoU kernels here still take bitmaps, not RLE.
 """
 import ctypes
 

@@ -1944,6 +1944,79 @@ def paste_masks(mask_logits, labels, boxes, count, thr, out_hw, out=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# COCO run-length encoding of masks on the GPU (csrc/pswin_rle.hip; rle.py states the format and holds the definitions)
+# ------------------------------------------------------------------------------------------------
+def rle_supported(n_masks, H, W, K=None, C=None):
+    """Whether the RLE kernels take the shape: H, W <= 65536 and H W < 2^32 (positions are uint32, pycocotools' own limit), fewer than
+    2^31 masks and, for the fused paste, its limits K <= 1024 and C <= 128."""
+    return 1 <= int(n_masks) < 1 << 31 and 1 <= int(H) <= 65536 and 1 <= int(W) <= 65536 and int(H) * int(W) < 1 << 32 and \
+        (K is None or 1 <= int(K) <= 1024) and (C is None or 1 <= int(C) <= 128)
+
+
+def _rle_workspace(N, H, W, dev):
+    key = ("rle_ws", N, H, W, _dev_key(dev))
+    if key not in _CACHE:
+        nbytes = ctypes.c_longlong(0)
+        _lib.check(_lib.load().pswin_rle_workspace(N, H, W, ctypes.byref(nbytes)), "pswin_rle_workspace")
+        _CACHE[key] = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+    return _CACHE[key]
+
+
+def rle_encode(masks, count=None, capacity=None, out=None):
+    """rle.encode_masks on the GPU (pswin_rle_encode): uint8 [N, H, W] or [B, K, H, W] masks -> rle.RleMasks.  count int32 [B] ON THE
+    DEVICE: rows past it are not read and own no runs.  Four launches whatever the batch holds; no atomics, no host synchronisation, no
+    host-to-device copy: the call can be captured.  The bit-planes and the scans live in one workspace per (N, H, W, device), every part of
+    it written by a call before the call reads it.  `out`: an RleMasks to reuse; nothing at or past `capacity` is written.  Limits:
+    rle_supported; beyond them PswinError.  CPU tensors: the definition."""
+    from . import rle
+    if not masks.is_cuda:
+        return rle.encode_masks_definition(masks, count, capacity, out)
+    N, B, K, H, W = rle._shape_nbk(masks, count)
+    dev = masks.device
+    if not rle_supported(N, H, W):
+        raise PswinError(f"rle_encode: outside the kernels' limits (H, W <= 65536, H W < 2^32, N < 2^31): {tuple(masks.shape)}")
+    if count is not None:
+        if count.device != dev:
+            raise PswinError("rle_encode: count must be on the device of the masks")
+        count = count.contiguous()
+    out = rle._out_for(out, N, H, W, dev, capacity, B, K, count, "rle_encode")
+    call("pswin_rle_encode", masks, ptr(masks), ptr(count), N, K or 1, H, W, ptr(out.offsets), ptr(out.runs), out.capacity,
+         ptr(_rle_workspace(N, H, W, dev)), algo_bytes=N * H * W)
+    return out
+
+
+def paste_masks_rle(mask_logits, labels, boxes, count, thr, out_hw, capacity=None, out=None):
+    """rle_encode(paste_masks(mask_logits, labels, boxes, count, thr, out_hw), count) without the bitmap (pswin_paste_masks_rle): the
+    column bits come from the paste's own sample -- the same float32 expression, compared with thr -- so the runs equal the bitmap
+    route's bit for bit.  Arguments as paste_masks (the logits' strides are passed on), capacity / out as rle_encode.  Four launches, no
+    atomics, no host synchronisation: capturable.  CPU tensors: the definition."""
+    from . import rle
+    if not mask_logits.is_cuda:
+        return rle.paste_masks_rle(mask_logits, labels, boxes, count, thr, out_hw, capacity, out)
+    H, W = int(out_hw[0]), int(out_hw[1])
+    if labels.dim() != 2 or mask_logits.dim() != 4 or tuple(mask_logits.shape[2:]) != (28, 28) or mask_logits.shape[0] != labels.numel() or \
+            tuple(boxes.shape) != tuple(labels.shape) + (4,):
+        raise PswinError(f"paste_masks_rle: mask_logits [B K, C, 28, 28], labels [B, K], boxes [B, K, 4], got {tuple(mask_logits.shape)}, "
+                         f"{tuple(labels.shape)}, {tuple(boxes.shape)}")
+    B, K, C = int(labels.shape[0]), int(labels.shape[1]), int(mask_logits.shape[1])
+    dev = mask_logits.device
+    if count.dtype != torch.int32 or tuple(count.shape) != (B,) or count.device != dev or labels.dtype != torch.int64:
+        raise PswinError("paste_masks_rle: count must be an int32 [B] tensor on the device of the logits, labels int64")
+    if not rle_supported(B * K, H, W, K, C) or B > 65535:
+        raise PswinError(f"paste_masks_rle: outside the kernels' limits (H, W <= 65536, H W < 2^32, K <= 1024, C <= 128, B <= 65535): "
+                         f"B = {B}, K = {K}, C = {C}, {H} x {W}")
+    lg = _lowp_or_f32(mask_logits.detach())
+    if min(lg.stride()) < 1:
+        lg = lg.contiguous()
+    labels, boxes, count = labels.contiguous(), boxes.detach().float().contiguous(), count.contiguous()
+    out = rle._out_for(out, B * K, H, W, dev, capacity, B, K, count, "paste_masks_rle")
+    sn, sc, sy, sx = (int(v) for v in lg.stride())
+    call("pswin_paste_masks_rle", lg, ptr(lg), dtype_code(lg), sn, sc, sy, sx, ptr(labels), ptr(boxes), ptr(count), B, K, C, H, W,
+         ctypes.c_float(float(thr)), ptr(out.offsets), ptr(out.runs), out.capacity, ptr(_rle_workspace(B * K, H, W, dev)))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # test-time augmentation: the merges of tta.py on the GPU (csrc/pswin_augtest.hip)
 # ------------------------------------------------------------------------------------------------
 def _aug_views(views):
