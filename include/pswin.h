@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSWIN_ABI_VERSION 10
+#define PSWIN_ABI_VERSION 11
 
 #define PSWIN_F32 0
 #define PSWIN_BF16 1
@@ -948,6 +948,33 @@ int pswin_rle_encode(const unsigned char* masks, const int32_t* count, long long
 int pswin_paste_masks_rle(const void* logits, int dtype, long long stride_n, long long stride_c, long long stride_y, long long stride_x,
                           const long long* labels, const float* boxes, const int32_t* count, int B, int K, int C, int H, int W, float thr,
                           long long* offsets, uint32_t* runs, long long capacity, void* workspace, void* stream);
+
+/* Intersections, areas and IoU of a padded batch's masks from their runs (csrc/pswin_rle_iou.hip; rle.py states the rule: rle_inter,
+ * inter_pairs_definition): the counterpart of pycocotools' rleArea / rleIou, and of pswin_mask_inter_pairs / pswin_mask_iou_pairs below,
+ * without bitmaps.  det_offsets int64 [B K + 1] / det_runs uint32 [det_capacity] and gt_offsets int64 [B G + 1] / gt_runs uint32
+ * [gt_capacity] as pswin_rle_encode lays them out (masks of H x W pixels, mask b K + k the detection k of image b); labels int64 and
+ * counts int32 as pswin_box_iou_pairs takes them.
+ * pswin_rle_inter_pairs writes every element of inter int32 [B][K][G] and areas int32 [B][K + G] exactly as pswin_mask_inter_pairs
+ * documents them; pswin_rle_iou_pairs stores what pswin_mask_iou_pairs stores: iou f32 [B][K][G] = float32(double(inter) / double(union)),
+ * 0 when the union is 0, -1 outside the pairs, and the areas as f32 [B][K] and [B][G], 0 past a count.  One device code for both.
+ * Overflow: a mask inside its count is whole when 0 <= offsets[n] <= offsets[n + 1] <= capacity; a mask that is not whole has area 0 and
+ * intersection 0 in its pairs, and overflow[0] = 1 is stored (overflow int32 [1]: the caller clears it; nothing else is written to it).
+ * No index >= capacity of runs is read, and every search stays inside the mask's own range, whatever the runs hold.
+ * Two launches for any batch and any data (the tables of both sides; the pairs), no atomics, no host synchronisation: the results are a
+ * function of the inputs alone.  A detection's tables of up to pswin_rle_inter_stage() entries are searched in LDS, longer ones in the
+ * workspace.  Limits: H W < 2^31, 1 <= B <= 65535, K <= 1024, G <= 512 (pswin_coco_supported), 1 <= capacity <= 2^40, at most 2^31 - 1
+ * runs per mask.  workspace: pswin_rle_inter_workspace bytes (8 bytes per unit of both capacities + 4 B (K + G)), 16-byte aligned; every
+ * part of it is written by a call before the call reads it.  Anything else is PSWIN_ERR_ARG, checked before the device is touched. */
+int pswin_rle_inter_stage(void);
+int pswin_rle_inter_workspace(int B, int K, int G, long long det_capacity, long long gt_capacity, long long* bytes);
+int pswin_rle_inter_pairs(const long long* det_offsets, const uint32_t* det_runs, long long det_capacity, const long long* det_labels,
+                          const int* det_count, const long long* gt_offsets, const uint32_t* gt_runs, long long gt_capacity,
+                          const long long* gt_labels, const int* gt_count, int B, int K, int G, int H, int W, int* inter, int* areas,
+                          int* overflow, void* workspace, void* stream);
+int pswin_rle_iou_pairs(const long long* det_offsets, const uint32_t* det_runs, long long det_capacity, const long long* det_labels,
+                        const int* det_count, const long long* gt_offsets, const uint32_t* gt_runs, long long gt_capacity,
+                        const long long* gt_labels, const int* gt_count, int B, int K, int G, int H, int W, float* iou, float* det_area,
+                        float* gt_area, int* overflow, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Detector training between "assigned" and "loss" for a padded batch (csrc/pswin_targets.hip;

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PSWIN_LIB") or os.path.join(_PKG, "libpswin_hip.so") 
 F32, BF16 = 0, 1
 MODE_PLANAR, MODE_PANO = 0, 1
 WS, WTOK, WPAD, HEAD_DIM = 7, 49, 64, 32
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -103,6 +103,12 @@ _PROTOTYPES = {
     "pswin_rle_encode": [_vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp, _vp, ctypes.c_longlong, _vp, _vp],
     "pswin_paste_masks_rle": [_vp, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i, _i,
                               _i, _f, _vp, _vp, ctypes.c_longlong, _vp, _vp],
+    "pswin_rle_inter_stage": [],
+    "pswin_rle_inter_workspace": [_i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _vp],
+    "pswin_rle_inter_pairs": [_vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp,
+                              _vp, _vp],
+    "pswin_rle_iou_pairs": [_vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp,
+                            _vp, _vp, _vp],
     "pswin_sample_rows_per_workgroup": [],
     "pswin_sample_workspace": [_i, _i, _i],
     "pswin_sample_ranks": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],

@@ -338,10 +338,12 @@ class PaddedTargets:
     """The annotations of a batch in buffers of a fixed shape, for a captured detector step: boxes f32 [B, Gmax, 4], labels int64
     [B, Gmax], count int32 [B] (the first count[b] rows of image b are boxes, the rest zeros) and masks uint8 [B, Gmax, H, W] or None
     (Faster R-CNN).  The captured step reads the buffers; `copy_from` puts the next batch into them, outside the capture and on the
-    stream the step is replayed on."""
+    stream the step is replayed on.  rle: the masks' COCO run-length encoding (rle.RleMasks of B Gmax masks, e.g.
+    RleMasks.from_lists(annotations, device, K=Gmax)) or None; only the mask metric of evaluation.py reads it, and allocate / of /
+    copy_from leave it alone."""
 
-    def __init__(self, boxes, labels, count, masks=None):
-        self.boxes, self.labels, self.count, self.masks = boxes, labels, count, masks
+    def __init__(self, boxes, labels, count, masks=None, rle=None):
+        self.boxes, self.labels, self.count, self.masks, self.rle = boxes, labels, count, masks, rle
         self.list_counts = None                      # of(lists): the host's copy of the counts, by which the RoI stage lays out its keys
 
     @classmethod

@@ -78,7 +78,7 @@ definitions bit for bit.
  7. SUMMARIZE, in numpy on the host: each statistic is the mean over the entries > -1, or -1: AP over all t (range 0, last m), at t = 0.5
     and 0.75 (found with np.isclose), for ranges 1, 2, 3; AR for range 0 at each of the first three max_dets, for ranges 1, 2, 3 at the
     last.  COCOeval's `scores` array, the 'proposal' route (useCats = 0) and JSON files are out of scope; the masks' RLE for
-    results files is rle.py (Detections.as_results), and the mask IoU kernels here still take bitmaps, not RLE.
+    results files is rle.py (Detections.as_results); the mask metric reads bitmaps or, by _mask_route's rule, the masks' RLE.
 """
 import ctypes
 
@@ -358,6 +358,70 @@ def _check_masks(dets, gts):
                          f"{tuple(gts.masks.shape)} {gts.masks.dtype}")
 
 
+def _mask_route(dets, gts):
+    """How the mask metric reads a batch's masks -- ONE rule for pair_iou_dispatch, mask / rle_inter_pairs_dispatch and both accumulators:
+    "bitmap" if both sides have bitmaps (dets.masks and targets.masks; the route and the bits it always had); otherwise "rle" if each side
+    has bitmaps or runs (dets.rle / targets.rle, rle.RleMasks) -- a side that has only bitmaps is encoded on the spot with
+    rle.encode_masks(masks, count), four launches and still capturable; otherwise the PswinError of _check_masks.  The sizes (height,
+    width) of the two sides must agree."""
+    d_rle, g_rle = getattr(dets, "rle", None), getattr(gts, "rle", None)
+    if (dets.masks is not None and gts.masks is not None) or (dets.masks is None and d_rle is None) or (gts.masks is None and g_rle is None):
+        _check_masks(dets, gts)
+        return "bitmap"
+    B, K, G = dets.labels.shape[0], dets.labels.shape[1], gts.labels.shape[1]
+    sizes = []
+    for who, side, rows in (("dets", dets, K), ("targets", gts, G)):
+        if side.masks is not None:
+            if side.masks.dtype != torch.uint8 or tuple(side.masks.shape[:2]) != (B, rows) or side.masks.dim() != 4:
+                raise PswinError(f"evaluation: {who}.masks must be uint8 [{B}, {rows}, H, W], got {side.masks.dtype} {tuple(side.masks.shape)}")
+            sizes.append(tuple(int(v) for v in side.masks.shape[2:]))
+        else:
+            enc = side.rle
+            if enc.offsets.numel() != B * rows + 1 or enc.offsets.dtype != torch.int64 or enc.runs.dtype != torch.uint32 or \
+                    enc.offsets.device != dets.labels.device or enc.runs.device != dets.labels.device or not enc.offsets.is_contiguous() or \
+                    not enc.runs.is_contiguous() or not 1 <= enc.capacity <= enc.runs.numel():
+                raise PswinError(f"evaluation: {who}.rle must hold int64 offsets [{B * rows + 1}] and uint32 runs of its capacity on "
+                                 f"{dets.labels.device}")
+            sizes.append((enc.height, enc.width))
+    if sizes[0] != sizes[1]:
+        raise PswinError(f"evaluation: masks of one size, got {sizes[0]} for the detections and {sizes[1]} for the targets")
+    return "rle"
+
+
+def _rle_sides(dets, gts):
+    """(det_rle, gt_rle) of the "rle" route: the side's runs, or its bitmaps encoded on the spot"""
+    from . import rle
+    d = dets.rle if dets.masks is None else rle.encode_masks(dets.masks.contiguous(), dets.count)
+    g = gts.rle if gts.masks is None else rle.encode_masks(gts.masks.contiguous(), gts.count)
+    return d, g
+
+
+def rle_inter_workspace(B, K, G, det_capacity, gt_capacity, device):
+    """a fresh workspace of pswin_rle_inter_workspace bytes for pswin_rle_inter_pairs / pswin_rle_iou_pairs"""
+    nbytes = ctypes.c_longlong(0)
+    _lib.check(_lib.load().pswin_rle_inter_workspace(B, K, G, int(det_capacity), int(gt_capacity), ctypes.byref(nbytes)),
+               "pswin_rle_inter_workspace")
+    return torch.empty(int(nbytes.value), dtype=torch.uint8, device=device)
+
+
+def _rle_pairs_args(dets, gts, d, g, who):
+    (B, K), G = dets.labels.shape, gts.labels.shape[1]
+    if not (1 <= B <= 65535 and 1 <= K <= COCO_MAX_K and 1 <= G <= COCO_MAX_G and d.height * d.width < 1 << 31):
+        raise PswinError(f"{who}: B = {B}, K = {K}, Gmax = {G}, {d.height} x {d.width} is outside the run-length kernels' limits "
+                         f"(K <= {COCO_MAX_K}, Gmax <= {COCO_MAX_G}, H W < 2^31)")
+    p = _lib.ptr
+    return (p(d.offsets), p(d.runs), d.capacity, p(dets.labels), p(dets.count), p(g.offsets), p(g.runs), g.capacity, p(gts.labels),
+            p(gts.count), B, K, G, d.height, d.width)
+
+
+def _iou_from_counts(inter, areas, K):
+    """mask_iou_pairs' float32 IoU and mask_areas' two f32 areas from inter_pairs' integers"""
+    da, ga = areas[:, :K].double(), areas[:, K:].double()
+    union = da[:, :, None] + ga[:, None, :] - inter.double()
+    iou = torch.where(union == 0, torch.zeros_like(union), inter.double() / union.clamp(min=1)).float()
+    return torch.where(inter < 0, torch.full_like(iou, -1.0), iou), da.float(), ga.float()
+
+
 def _out(out, shape, dtype, device, what):
     """`out` after a check of its shape, or a fresh buffer"""
     if out is None:
@@ -367,15 +431,23 @@ def _out(out, shape, dtype, device, what):
     return out
 
 
-def pair_iou_dispatch(dets, gts, iou="bbox", out=None):
-    """(iou f32 [B, K, Gmax], det_area f32 [B, K], gt_area f32 [B, Gmax]) of the box or the mask metric.  On the GPU: pswin_box_iou_pairs
-    or pswin_mask_iou_pairs, into the three buffers of `out` if given; on the CPU the definitions."""
+def pair_iou_dispatch(dets, gts, iou="bbox", out=None, rle_overflow=None):
+    """(iou f32 [B, K, Gmax], det_area f32 [B, K], gt_area f32 [B, Gmax]) of the box or the mask metric.  On the GPU: pswin_box_iou_pairs,
+    pswin_mask_iou_pairs or, by _mask_route's rule, pswin_rle_iou_pairs on the masks' runs, into the three buffers of `out` if given; on
+    the CPU the definitions.  rle_overflow: an int32 [1] flag on the device that the run-length route sets when a run pool was too small
+    (rle.inter_pairs_definition says what the results are then); it is never cleared here."""
     _check_batch(dets, gts)
+    route = None
     if iou == "segm":
-        _check_masks(dets, gts)
+        route = _mask_route(dets, gts)
     elif iou != "bbox":
         raise PswinError(f"evaluation: iou must be 'bbox' or 'segm', got {iou!r}")
     if not dets.labels.is_cuda:
+        if route == "rle":
+            inter, areas, over = rle_inter_pairs_dispatch(dets, gts)
+            if rle_overflow is not None:
+                rle_overflow |= over
+            return _iou_from_counts(inter, areas, dets.labels.shape[1])
         if iou == "segm":
             return (mask_iou_pairs(dets, gts),) + mask_areas(dets, gts)
         return box_iou_pairs(dets, gts), box_areas(dets.boxes), box_areas(gts.boxes)
@@ -384,7 +456,13 @@ def pair_iou_dispatch(dets, gts, iou="bbox", out=None):
     out = _out(bufs[0], (B, K, G), torch.float32, dev, "pair_iou_dispatch")
     det_area, gt_area = _out(bufs[1], (B, K), torch.float32, dev, "pair_iou_dispatch"), _out(bufs[2], (B, G), torch.float32, dev, "pair_iou_dispatch")
     p = _lib.ptr
-    if iou == "segm":
+    if route == "rle":
+        d, g = _rle_sides(dets, gts)
+        args = _rle_pairs_args(dets, gts, d, g, "pair_iou_dispatch")
+        over = torch.zeros(1, dtype=torch.int32, device=dev) if rle_overflow is None else _out(rle_overflow, (1,), torch.int32, dev, "pair_iou_dispatch")
+        ws = rle_inter_workspace(B, K, G, d.capacity, g.capacity, dev)
+        _lib.call("pswin_rle_iou_pairs", out, *args, p(out), p(det_area), p(gt_area), p(over), p(ws), algo_bytes=12 * (d.capacity + g.capacity))
+    elif iou == "segm":
         dm, gm = dets.masks.contiguous(), gts.masks.contiguous()
         H, W = dm.shape[2:]
         n = _lib.load().pswin_mask_iou_workspace(B, K, G)
@@ -424,6 +502,10 @@ def ap_segments_dispatch(marks_sorted, bounds, num_gts, out=None):
     return ap
 
 
+_RLE_OVERFLOW = ("{}: a run pool was too small for its masks (RleMasks.offsets[N] > capacity), so masks were scored as empty; produce the "
+                 "runs again with a larger capacity (heads_predict's rle_capacity, encode_masks' capacity)")
+
+
 class MapAccumulator:
     """mAP over a data set, batch by batch, in buffers of a fixed shape on `device`.  iou_thrs: T thresholds; scale_ranges: None or S
     pairs as the reference's eval_map takes them (their squares bound the areas); capacity_images: the image slots; max_per_img: K, the
@@ -452,10 +534,12 @@ class MapAccumulator:
         self.num_gts = torch.zeros(self.S, self.C, dtype=torch.int32, device=dev)
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.rle_overflow = torch.zeros(1, dtype=torch.int32, device=dev)          # set by the run-length route of "segm" (_mask_route)
 
     def reset(self):
         """Forget every record, in place (stream-ordered; the buffers keep their addresses for a captured update)."""
         self.rec_score.zero_(), self.rec_marks.zero_(), self.num_gts.zero_(), self.cursor.zero_(), self.overflow.zero_()
+        self.rle_overflow.zero_()
         self.rec_label.fill_(self.C)
         return self
 
@@ -472,7 +556,7 @@ class MapAccumulator:
             raise PswinError(f"MapAccumulator.update: detections [{B}, {K}] on {dets.labels.device}, the accumulator holds max_per_img = "
                              f"{self.K} on {self.cursor.device}")
         ignore = _flags(ignore, gts)
-        iou, det_area, gt_area = pair_iou_dispatch(dets, gts, self.iou)
+        iou, det_area, gt_area = pair_iou_dispatch(dets, gts, self.iou, rle_overflow=self.rle_overflow)
         G = gts.labels.shape[1]
         if not iou.is_cuda:
             marks = match_pairs(iou, dets, gts, ignore, self.iou_thrs, self.area_ranges, det_area, gt_area)
@@ -503,6 +587,8 @@ class MapAccumulator:
         over the classes with num_gts > 0, or 0.0 if there are none, as the reference reports it."""
         if int(self.overflow):
             raise PswinError(f"MapAccumulator: more than capacity_images = {self.capacity} images were given; the records past it are lost")
+        if int(self.rle_overflow):
+            raise PswinError(_RLE_OVERFLOW.format("MapAccumulator"))
         order, bounds = sort_records(self.rec_score.reshape(-1), self.rec_label.reshape(-1), self.C)
         marks_sorted = self.rec_marks.reshape(self.T, self.S, -1).index_select(2, order)
         ap = ap_segments_dispatch(marks_sorted, bounds, self.num_gts).cpu()
@@ -719,12 +805,17 @@ def _crowd_flags(crowd, gts):
     return crowd.bool()
 
 
-def coco_pair_iou(dets, gts, crowd=None, iou="bbox"):
+def coco_pair_iou(dets, gts, crowd=None, iou="bbox", mask_counts=None):
     """(iou f64 [B, K, Gmax], det_area f64 [B, K], gt_area f64 [B, Gmax]) by rule 2 and 3: for the pairs with k < dets.count[b],
     g < gts.count[b] and equal labels inter / union in double, the union being the detection's area alone for a crowd box; -1 for every
-    other pair.  Boxes: x, y, w = x2 - x1, h = y2 - y1 of the float32 corners widened to double; masks: integer pixel counts."""
+    other pair.  Boxes: x, y, w = x2 - x1, h = y2 - y1 of the float32 corners widened to double; masks: integer pixel counts, from the
+    bitmaps or, if given, from mask_counts = (inter, areas) as mask_inter_pairs / rle.inter_pairs_definition return them."""
     cr = _crowd_flags(crowd, gts)
-    if iou == "segm":
+    if iou == "segm" and mask_counts is not None:
+        K = dets.labels.shape[1]
+        inter = mask_counts[0].clamp(min=0).double()
+        da, ga = mask_counts[1][:, :K].double(), mask_counts[1][:, K:].double()
+    elif iou == "segm":
         d, g = (dets.masks != 0).flatten(2), (gts.masks != 0).flatten(2)
         inter = torch.matmul(d.double(), g.double().transpose(1, 2))              # sums of 0 / 1 in double: exact
         da, ga = d.sum(2).double(), g.sum(2).double()
@@ -987,6 +1078,36 @@ def mask_inter_pairs_dispatch(dets, gts, out=None):
     return inter, areas
 
 
+def rle_inter_pairs_dispatch(dets, gts, out=None, workspace=None):
+    """(inter int32 [B, K, Gmax], areas int32 [B, K + Gmax], overflow int32 [1]): mask_inter_pairs from the masks' runs, for a batch that
+    _mask_route sends the run-length way (dets.rle / targets.rle; a side that has only bitmaps is encoded on the spot).  On the GPU
+    pswin_rle_inter_pairs (two launches, no host synchronisation: capturable), into the three buffers of `out` if given -- a given
+    overflow flag is set, never cleared -- and with `workspace` (rle_inter_workspace) if the caller keeps one; on the CPU
+    rle.inter_pairs_definition, which also says what a pool that was too small does to the results."""
+    from . import rle
+    _check_batch(dets, gts)
+    if _mask_route(dets, gts) != "rle":
+        raise PswinError("rle_inter_pairs_dispatch: both sides have bitmaps; that batch goes to mask_inter_pairs_dispatch")
+    d, g = _rle_sides(dets, gts)
+    bufs = out or (None, None, None)
+    if not dets.labels.is_cuda:
+        inter, areas, over = rle.inter_pairs_definition(d, dets.labels, dets.count, g, gts.labels, gts.count)
+        if bufs[2] is not None:
+            flag = bufs[2]
+            flag |= over                                   # in place: the caller's flag is set, never cleared
+            over = flag
+        return inter, areas, over
+    (B, K), G, dev = dets.labels.shape, gts.labels.shape[1], dets.labels.device
+    args = _rle_pairs_args(dets, gts, d, g, "rle_inter_pairs_dispatch")
+    inter = _out(bufs[0], (B, K, G), torch.int32, dev, "rle_inter_pairs_dispatch")
+    areas = _out(bufs[1], (B, K + G), torch.int32, dev, "rle_inter_pairs_dispatch")
+    over = torch.zeros(1, dtype=torch.int32, device=dev) if bufs[2] is None else _out(bufs[2], (1,), torch.int32, dev, "rle_inter_pairs_dispatch")
+    ws = rle_inter_workspace(B, K, G, d.capacity, g.capacity, dev) if workspace is None else workspace
+    p = _lib.ptr
+    _lib.call("pswin_rle_inter_pairs", inter, *args, p(inter), p(areas), p(over), p(ws), algo_bytes=12 * (d.capacity + g.capacity))
+    return inter, areas, over
+
+
 class CocoAccumulator:
     """bbox / segm mAP and AR by the COCO protocol over a data set, batch by batch, in buffers of a fixed shape on `device` (the rules:
     the module docstring).  iou_thrs: None (the reference's ten) or T thresholds in (0, 1]; max_dets: 1 to 4 ascending caps per (image,
@@ -1023,12 +1144,14 @@ class CocoAccumulator:
         self.num_gts = torch.zeros(self.A, self.C, dtype=torch.int32, device=dev)
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.rle_overflow = torch.zeros(1, dtype=torch.int32, device=dev)          # set by the run-length route of "segm" (_mask_route)
         self._thrs = _doubles(self.iou_thrs)
         self._ranges = _doubles([v for r in self.area_ranges for v in r])
 
     def reset(self):
         """Forget every record, in place (stream-ordered; the buffers keep their addresses for a captured update)."""
         self.rec_score.zero_(), self.rec_rank.zero_(), self.rec_flags.zero_(), self.num_gts.zero_(), self.cursor.zero_(), self.overflow.zero_()
+        self.rle_overflow.zero_()
         self.rec_label.fill_(self.C)
         return self
 
@@ -1036,7 +1159,8 @@ class CocoAccumulator:
         """Score one batch: flags uint8 [T, A, B, K] (FLAG_MATCHED | FLAG_IGNORED), and the batch's records appended at the cursor, which
         advances by B.  dets: a Detections with K = max_per_img rows; targets: a PaddedTargets, or the list form, padded on entry; crowd:
         bool [B, Gmax] or None; gt_area: f32 / f64 [B, Gmax] or None (the annotations' area; None: the box's or the mask's own).  On the
-        GPU ONE launch for boxes (pswin_coco_match), three for masks (pswin_mask_inter_pairs' two in front), no host synchronisation and
+        GPU ONE launch for boxes (pswin_coco_match), three for masks (pswin_mask_inter_pairs' two in front, or by _mask_route's rule
+        pswin_rle_inter_pairs' two on the masks' runs, which sets rle_overflow when a run pool was too small), no host synchronisation and
         no data-dependent shape: it can be captured with the prediction.  A shape outside coco_supported raises before any launch.
         Image slots at or past the capacity are not written; accumulate() raises then.  out: a buffer for the flags, if the caller keeps one."""
         gts = PaddedTargets.of(targets)
@@ -1046,8 +1170,7 @@ class CocoAccumulator:
             raise PswinError(f"CocoAccumulator.update: detections [{B}, {K}] on {dets.labels.device}, the accumulator holds max_per_img = "
                              f"{self.K} on {dev}")
         _check_batch(dets, gts)
-        if self.iou == "segm":
-            _check_masks(dets, gts)
+        route = _mask_route(dets, gts) if self.iou == "segm" else None
         crowd = _flags(crowd, gts)
         G = gts.labels.shape[1]
         if gt_area is not None:
@@ -1055,7 +1178,10 @@ class CocoAccumulator:
                 raise PswinError(f"CocoAccumulator.update: gt_area must be f32 or f64 {tuple(gts.labels.shape)} on {dev}")
             gt_area = gt_area.double().contiguous()
         if not dev.type == "cuda":
-            iou, det_area, own_area = coco_pair_iou(dets, gts, crowd, self.iou)
+            counts = None
+            if route == "rle":
+                counts = rle_inter_pairs_dispatch(dets, gts, out=(None, None, self.rle_overflow))[:2]
+            iou, det_area, own_area = coco_pair_iou(dets, gts, crowd, self.iou, counts)
             area = own_area if gt_area is None else gt_area
             flags, rank = coco_match(iou, dets, gts, crowd, det_area, area, self.iou_thrs, self.area_ranges, self.C)
             if out is not None:
@@ -1078,7 +1204,9 @@ class CocoAccumulator:
             flags = _out(out, (self.T, self.A, B, K), torch.uint8, dev, "CocoAccumulator.update")
             p = _lib.ptr
             inter = areas = None
-            if self.iou == "segm":
+            if route == "rle":
+                inter, areas = rle_inter_pairs_dispatch(dets, gts, out=(None, None, self.rle_overflow))[:2]
+            elif route == "bitmap":
                 inter, areas = mask_inter_pairs_dispatch(dets, gts)
             _lib.call("pswin_coco_match", flags, p(dets.boxes), p(dets.scores), p(dets.labels), p(dets.count), p(gts.boxes), p(gts.labels),
                       p(gts.count), p(crowd), p(gt_area), p(inter), p(areas), self._thrs, self.T, self._ranges, self.A, B, K, G, self.C,
@@ -1092,6 +1220,8 @@ class CocoAccumulator:
         (class, range) has no counted box."""
         if int(self.overflow):
             raise PswinError(f"CocoAccumulator: more than capacity_images = {self.capacity} images were given; the records past it are lost")
+        if int(self.rle_overflow):
+            raise PswinError(_RLE_OVERFLOW.format("CocoAccumulator"))
         return coco_accumulate_dispatch(self.rec_score, self.rec_label, self.rec_rank, self.rec_flags, self.num_gts, self.max_dets, self.C)
 
     def summarize(self, ev=None):

@@ -17,10 +17,20 @@ The rules below are stated completely and restated independently as plain loops 
     signed value, five bits at a time, low bits first: c = x & 0x1f; x >>= 5 (arithmetic); more = (x != -1) if (c & 0x10) else (x != 0);
     if more: c |= 0x20; the character is c + 48.  At most 7 characters per run.  Reading undoes it: the last group's bit 0x10 extends the sign.
   rle_decode, rle_area: the bitmap back, and the sum of the odd-indexed counts.
+  rle_inter (the integer part of rleIou).  For one mask with counts c[0 .. n): p[i] = c[0] + ... + c[i], f[i] = the sum of the odd-indexed
+    c[j], j <= i, and p[-1] = f[-1] = 0.  For a position x in [0, H W], i(x) is the number of i with p[i] <= x (an upper bound), and
+    F(x) = f[i - 1] + (x - p[i - 1] if i is odd and i < n else 0) is the number of foreground positions below x.  Then
+    rle_area(c) = f[n - 1] and rle_inter(cd, cg) = the sum over the odd i of cd of F_g(p_d[i]) - F_g(p_d[i - 1]).  Integers only, so the
+    order of the sum does not matter; zero-length runs (a leading c[0] = 0, or runs of 0 inside foreign RLE such as [0, 3, 0, 2, 4, 0, 1])
+    need no special case.  The IoU is float32(double(inter) / double(area_d + area_g - inter)), 0 when the union is 0, as for bitmaps
+    (evaluation.mask_iou_pairs).  tests/_rle_iou_cases.py restates it as the two-pointer loop of rleIou.
+  inter_pairs_definition: rle_inter and rle_area over the same-class pairs of a padded batch, in the layout of
+    evaluation.mask_inter_pairs.  HIP tensors: csrc/pswin_rle_iou.hip through evaluation.rle_inter_pairs_dispatch.
 
 RleMasks holds the runs of N masks in buffers of a fixed shape (the RLE counterpart of Detections / PaddedTargets), so that a captured
-inference step can produce them; the strings are made on the host when results are read back (to_lists): producing them on the device is
-out of scope, and so are RLE inputs to the mask IoU kernels, a fused form for test-time augmentation and polygon / frPyObjects decoding.
+inference step can produce them and a captured scoring step can read them; the strings are made on the host when results are read back
+(to_lists) and parsed on the host (from_lists): producing them on the device is out of scope, and so are a fused form for test-time
+augmentation and polygon / frPyObjects decoding.
 """
 import numpy as np
 import torch
@@ -95,6 +105,24 @@ def rle_area(counts):
     return int(np.asarray(counts, dtype=np.int64)[1::2].sum())
 
 
+def _fg_below(p, f, x):
+    """F(x) of the module docstring for the tables (p, f) of one mask, at every position of the array x"""
+    n = p.size
+    i = np.searchsorted(p, x, side="right")                                    # the number of p[i] <= x
+    pp, ff = np.concatenate([[0], p]), np.concatenate([[0], f])                # shifted by one: pp[i] = p[i - 1]
+    return ff[i] + np.where(((i & 1) == 1) & (i < n), x - pp[i], 0)
+
+
+def rle_inter(cd, cg):
+    """The number of positions that are foreground in both masks, from their counts alone (the module docstring states the rule)"""
+    cd, cg = np.asarray(cd, dtype=np.int64).reshape(-1), np.asarray(cg, dtype=np.int64).reshape(-1)
+    pd, pg = np.cumsum(cd), np.cumsum(cg)
+    fg = np.cumsum(np.where(np.arange(cg.size) & 1, cg, 0))
+    ends = pd[1::2]
+    starts = pd[0::2][:ends.size]                                              # p_d[i - 1] for the odd i
+    return int((_fg_below(pg, fg, ends) - _fg_below(pg, fg, starts)).sum())
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # the runs of a batch
 # ------------------------------------------------------------------------------------------------------------------------
@@ -138,6 +166,41 @@ class RleMasks:
                              f"a larger capacity")
         runs = self.runs[:max(int(off[-1]), 1)].cpu().numpy()
         return [runs[off[n]:off[n + 1]] for n in range(off.size - 1)]
+
+    @classmethod
+    def from_lists(cls, lists, device, K=None):
+        """The inverse of to_lists(): per image a list of {"size": [H, W], "counts": bytes (pycocotools' string) or a sequence of ints} ->
+        an RleMasks with B = len(lists), K (default: the largest count, at least 1), count int32 [B] and a pool of exactly the runs'
+        total (at least 1).  Checked on the host: one size for all masks, runs that sum to H W, at most K masks per image.
+        from_lists(x.to_lists(), ...) has x's offsets and x's runs below offsets[N]."""
+        B = len(lists)
+        counts = [len(per) for per in lists]
+        K = max([1] + counts) if K is None else int(K)
+        if B < 1 or K < 1 or max(counts) > K:
+            raise PswinError(f"RleMasks.from_lists: {B} images with {counts} masks do not fit K = {K}")
+        size, per_mask = None, []
+        for per in lists:
+            for d in per:
+                hw = tuple(int(v) for v in d["size"])
+                size = hw if size is None else size
+                if len(hw) != 2 or hw != size or min(hw) < 1:
+                    raise PswinError(f"RleMasks.from_lists: masks of one size [H, W], got {list(hw)} after {list(size)}")
+                c = d["counts"]
+                c = rle_from_string(c) if isinstance(c, (bytes, bytearray)) else np.asarray(c, dtype=np.int64).reshape(-1)
+                if c.size and (int(c.min()) < 0 or int(c.max()) > 0xffffffff):
+                    raise PswinError("RleMasks.from_lists: counts are uint32")
+                if int(c.astype(np.int64).sum()) != hw[0] * hw[1]:
+                    raise PswinError(f"RleMasks.from_lists: the runs sum to {int(c.astype(np.int64).sum())}, not to {hw[0]} x {hw[1]}")
+                per_mask.append(c.astype(np.uint32))
+            per_mask += [np.zeros(0, dtype=np.uint32)] * (K - len(per))
+        if size is None:
+            raise PswinError("RleMasks.from_lists: no mask gives the size")
+        total = sum(c.size for c in per_mask)
+        host = cls.allocate(B * K, size[0], size[1], "cpu", max(total, 1), B, K, torch.tensor(counts, dtype=torch.int32))
+        _fill(host, per_mask)
+        if total == 0:
+            host.runs.zero_()
+        return cls(host.offsets.to(device), host.runs.to(device), size[0], size[1], host.capacity, B, K, host.count.to(device))
 
     def to_lists(self):
         """Per image (one image when the masks are no detections) a list of {"size": [H, W], "counts": bytes}, one per detection row in row
@@ -227,3 +290,57 @@ def paste_masks_rle(mask_logits, labels, boxes, count, thr, out_hw, capacity=Non
     from . import detector
     masks = detector.paste_masks_batch(mask_logits, labels, boxes, count, thr, out_hw)
     return encode_masks_definition(masks, count.to(torch.int32), capacity, out)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# intersections and areas of a padded batch, from the runs
+# ------------------------------------------------------------------------------------------------------------------------
+def _counts_of_side(enc, count, B, rows, who):
+    """per mask (b, row): its counts; an empty array for a row past the count; None for a mask inside the count that is not whole"""
+    if enc.offsets.numel() != B * rows + 1:
+        raise PswinError(f"inter_pairs_definition: {who} holds {enc.offsets.numel() - 1} masks, the batch has {B} x {rows}")
+    off = enc.offsets.cpu().numpy()
+    runs = enc.runs.cpu().numpy()[:enc.capacity]
+    live = np.clip(count.cpu().numpy().astype(np.int64), 0, rows)
+    out = []
+    for b in range(B):
+        for r in range(rows):
+            o0, o1 = int(off[b * rows + r]), int(off[b * rows + r + 1])
+            if r >= live[b]:
+                out.append(np.zeros(0, dtype=np.int64))
+            elif 0 <= o0 <= o1 <= enc.capacity:
+                out.append(runs[o0:o1].astype(np.int64))
+            else:
+                out.append(None)
+    return out
+
+
+def inter_pairs_definition(det_rle, det_labels, det_count, gt_rle, gt_labels, gt_count):
+    """(inter int32 [B, K, G], areas int32 [B, K + G], overflow int32 [1]) from two RleMasks of one size, with the layout and the -1 / 0
+    conventions of evaluation.mask_inter_pairs: inter is rle_inter for the pairs with k < det_count[b], g < gt_count[b] (both clamped) and
+    equal labels, -1 for every other pair; areas are rle_area of image b's detections (first K) and boxes (last G), 0 past a count.
+    Overflow: a mask inside its count is whole when 0 <= offsets[n] <= offsets[n + 1] <= capacity; one that is not has area 0 and
+    intersection 0 in its pairs, nothing of it is read, and overflow is 1."""
+    (B, K), G = det_labels.shape, gt_labels.shape[1]
+    if (det_rle.height, det_rle.width) != (gt_rle.height, gt_rle.width):
+        raise PswinError(f"inter_pairs_definition: masks of {det_rle.height} x {det_rle.width} against {gt_rle.height} x {gt_rle.width}")
+    d = _counts_of_side(det_rle, det_count, B, K, "det_rle")
+    g = _counts_of_side(gt_rle, gt_count, B, G, "gt_rle")
+    dl, gl = det_labels.cpu().numpy(), gt_labels.cpu().numpy()
+    dn, gn = np.clip(det_count.cpu().numpy().astype(np.int64), 0, K), np.clip(gt_count.cpu().numpy().astype(np.int64), 0, G)
+    inter = np.full((B, K, G), -1, dtype=np.int64)
+    areas = np.zeros((B, K + G), dtype=np.int64)
+    overflow = int(any(c is None for c in d + g))
+    for b in range(B):
+        for k in range(dn[b]):
+            cd = d[b * K + k]
+            areas[b, k] = 0 if cd is None else rle_area(cd)
+        for j in range(gn[b]):
+            cg = g[b * G + j]
+            areas[b, K + j] = 0 if cg is None else rle_area(cg)
+        for k in range(dn[b]):
+            for j in range(gn[b]):
+                if dl[b, k] == gl[b, j]:
+                    cd, cg = d[b * K + k], g[b * G + j]
+                    inter[b, k, j] = 0 if cd is None or cg is None else rle_inter(cd, cg)
+    return torch.from_numpy(inter.astype(np.int32)), torch.from_numpy(areas.astype(np.int32)), torch.tensor([overflow], dtype=torch.int32)
