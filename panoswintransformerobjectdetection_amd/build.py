@@ -60,6 +60,24 @@ def build(force=False, verbose=True):
     return lib
 
 
+# libpswin_poly_hip.so (include/pswin_poly.h): the polygon rasteriser, one source, a library of its own
+POLY_SRC = os.path.join(CSRC, "pswin_poly.hip")
+POLY_LIB = os.path.join(PKG, "libpswin_poly_hip.so")
+
+
+def build_poly(force=False, verbose=True):
+    deps = [POLY_SRC, os.path.join(ROOT, "include", "pswin_poly.h"), os.path.join(ROOT, "include", "pswin.h"),
+            os.path.join(CSRC, "pswin_common.hpp"), os.path.join(CSRC, "pswin_detect_post.hpp")]
+    if not force and os.path.exists(POLY_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(POLY_LIB) for d in deps):
+        return POLY_LIB
+    cmd = [HIPCC] + FLAGS + ["-shared", POLY_SRC, "-o", POLY_LIB]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return POLY_LIB
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
-    print("built", LIB)
+    build_poly(force="--force" in sys.argv)
+    print("built", LIB, POLY_LIB)

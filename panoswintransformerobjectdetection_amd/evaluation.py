@@ -549,7 +549,8 @@ class MapAccumulator:
         host read, of the lists' box counts); ignore: bool [B, Gmax] or None.  No host synchronisation and no data-dependent shape: it
         can be captured with the prediction.  An image without detections and boxes contributes nothing, so a short last batch is padded
         with such images.  Image slots at or past the capacity are not written; summarize() raises then.  out: the GPU path's buffer for
-        the marks, if the caller keeps one."""
+        the marks, if the caller keeps one.  Polygon ground truth for iou="segm": targets.rle = polygons.polygons_to_rle(PolygonBatch) is
+        an RleMasks like any other."""
         gts = PaddedTargets.of(targets)
         B, K = dets.labels.shape
         if K != self.K or dets.labels.device != self.cursor.device:
@@ -1162,7 +1163,8 @@ class CocoAccumulator:
         GPU ONE launch for boxes (pswin_coco_match), three for masks (pswin_mask_inter_pairs' two in front, or by _mask_route's rule
         pswin_rle_inter_pairs' two on the masks' runs, which sets rle_overflow when a run pool was too small), no host synchronisation and
         no data-dependent shape: it can be captured with the prediction.  A shape outside coco_supported raises before any launch.
-        Image slots at or past the capacity are not written; accumulate() raises then.  out: a buffer for the flags, if the caller keeps one."""
+        Image slots at or past the capacity are not written; accumulate() raises then.  out: a buffer for the flags, if the caller keeps one.
+        Polygon ground truth: targets.rle = polygons.polygons_to_rle(PolygonBatch) is an RleMasks like any other."""
         gts = PaddedTargets.of(targets)
         B, K = dets.labels.shape
         dev = self.cursor.device

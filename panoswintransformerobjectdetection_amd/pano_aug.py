@@ -797,7 +797,8 @@ class PanoTrainTransform:
         detector.PaddedTargets: boxes, labels and count filled by one copy each, masks (uint8 [B, Gmax, Hp, Wp], the padded input's
         resolution) by one launch of pswin_pano_masks (warp_resize_masks), every byte.  masks: a list of per-image [n_i, H, W] uint8
         arrays or tensors, one bitmap per input box, or one packed device tensor [B, Gin, H, W] (rows past an image's boxes are
-        ignored); None gives targets.masks = None, the Faster R-CNN form.  out: a PaddedTargets to write in place (its max_gt must
+        ignored), or a polygons.PolygonBatch of the images' size whose object k of image b belongs to box k (rasterised once by
+        polygons_to_masks, then the packed-tensor route); None gives targets.masks = None, the Faster R-CNN form.  out: a PaddedTargets to write in place (its max_gt must
         hold the batch's rows and its masks have this batch's padded size); None allocates one with Gmax = the largest count, at
         least 1."""
         from .detector import PaddedTargets
@@ -841,7 +842,14 @@ class PanoTrainTransform:
 
     @staticmethod
     def _pack_masks(masks, n_in, B, H, W, dev, what):
-        """The source bitmaps as one device uint8 [B, Gin, H, W] tensor: a packed tensor as it is, a list padded with zero planes."""
+        """The source bitmaps as one device uint8 [B, Gin, H, W] tensor: a packed tensor as it is, a list padded with zero planes, a
+        polygons.PolygonBatch rasterised once (polygons_to_masks: on the GPU two launches and no bitmap upload)."""
+        from .polygons import PolygonBatch, polygons_to_masks
+        if isinstance(masks, PolygonBatch):
+            if masks.xy.device != dev or masks.B != B or (masks.height, masks.width) != (H, W) or masks.K < max(1, max(n_in)):
+                raise PswinError(f"{what}: the PolygonBatch must hold {B} images of {H} x {W} on {dev} with K >= every image's boxes "
+                                 f"({max(n_in)}); got B = {masks.B}, K = {masks.K}, {masks.height} x {masks.width} on {masks.xy.device}")
+            return polygons_to_masks(masks)
         if isinstance(masks, torch.Tensor):
             if not masks.is_cuda or masks.device != dev or masks.dtype != torch.uint8 or masks.dim() != 4 or masks.shape[0] != B \
                     or tuple(masks.shape[2:]) != (H, W) or masks.shape[1] < max(1, max(n_in)):

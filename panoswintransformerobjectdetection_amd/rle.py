@@ -29,8 +29,8 @@ The rules below are stated completely and restated independently as plain loops 
 
 RleMasks holds the runs of N masks in buffers of a fixed shape (the RLE counterpart of Detections / PaddedTargets), so that a captured
 inference step can produce them and a captured scoring step can read them; the strings are made on the host when results are read back
-(to_lists) and parsed on the host (from_lists): producing them on the device is out of scope, and so are a fused form for test-time
-augmentation and polygon / frPyObjects decoding.
+(to_lists) and parsed on the host (from_lists): producing them on the device is out of scope, and so is a fused form for test-time
+augmentation.  Polygon annotations (frPyObjects) become RleMasks through polygons.polygons_to_rle.
 """
 import numpy as np
 import torch
